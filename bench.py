@@ -12,16 +12,22 @@ N > 1:  one process per GPU: under torch.distributed.run (WORLD_SIZE set, which 
         gets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT; the parent exits non-zero if
         any rank fails, or with RCCL if fewer than N devices are visible).  The library's own RCCL communicator
         does the all-reduces over xGMI, enqueued on the stream by dist.hip; the line reports the ranks RCCL
-        itself counts (ncclCommCount) and each rank's kernel and all-reduce time.  The headline splits ROWS:
-        each rank spreads its own n/N points for all 32 windows, the 32x64 oversampled grids (16 KB) are
-        all-reduced, each rank interpolates its own rows.  The line also carries the split BASELINE
+        itself counts (ncclCommCount) and, with --full, each rank's kernel and all-reduce time.  The headline
+        splits ROWS: each rank spreads its own n/N points for all 32 windows, the 32x64 oversampled grids (16 KB)
+        are all-reduced, each rank interpolates its own rows.  With --full the line also carries the split BASELINE
         configs[3] names, 4 COMPONENTS per GPU (y, 8 MB, all-reduced), timed the same way
         ("partition_components").  Total work is fixed -> "scaling": "strong".
 
-Printed (rank 0): one JSON line with value = whole-job matvecs/s, the roofline of the dominant kernel
-(measured live with hipEvents on the library stream), the CPU baseline (this repo's C/OpenMP
-restatement of the reference NFFT path = oracle/, "kind": "port", on a bounded sample), and PCG
-time to 1e-6 (unpreconditioned, N = 1).
+A plain run (`--gpus N --steps K --warmup W`) sets up, pre-warms, runs the W warmup and the K timed steps and
+prints (rank 0) one JSON line with value = whole-job matvecs/s and ms_per_step.  `--dump-outputs DIR` also
+writes the y of the last timed step (DIR/y.npy, float64; the inputs are seeded, so two builds can be compared
+entry for entry).
+
+With `--full` the line also carries the roofline of the dominant kernel (an instrumented repeat of the timed
+steps with hipEvents on the library stream, and the PMC passes), the CPU baseline (this repo's C/OpenMP
+restatement of the reference NFFT path = oracle/, "kind": "port", on a bounded sample), the PCG / FGMRES / loss
+legs (N = 1: with the Nystrom and AFN preconditioners), configs B and E and, for N > 1, the other partition and
+the all-reduce comparison of the peer-memory exchange.
 """
 from __future__ import annotations
 
@@ -85,10 +91,16 @@ def host_info():
             "omp_env": {k: os.environ.get(k) for k in ("OMP_NUM_THREADS", "OMP_PROC_BIND", "OMP_PLACES")}}
 
 
+def scratch_dir():
+    """Where the --full legs keep their by-products (the -march=native oracle, the PMC passes' csv): the folder
+    NFFT4GP_OUT names, else bench_out/ beside this file (git-ignored); tools/*.sh write there too."""
+    return os.path.abspath(os.environ.get("NFFT4GP_OUT") or os.path.join(ROOT, "bench_out"))
+
+
 def _native_oracle():
     """A -march=native build of the oracle for this host (built into a scratch dir), or None."""
     try:
-        out_dir = os.path.join(ROOT, "gpurun_out", "oracle_native")
+        out_dir = os.path.join(scratch_dir(), "oracle_native")
         os.makedirs(out_dir, exist_ok=True)
         so = os.path.join(out_dir, "liboracle_native.so")
         subprocess.run(["gcc", "-O3", "-march=native", "-fPIC", "-fopenmp", "-std=gnu11", "-shared",
@@ -359,7 +371,7 @@ def pmc_traffic(n, d, timeout=600, precision=64):
     if exe is None:
         return None
     out = {}
-    base = os.path.join(ROOT, "gpurun_out", "bench_pmc")
+    base = os.path.join(scratch_dir(), "bench_pmc")
     env = dict(os.environ, TMPDIR="/tmp")
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d_out = os.path.join(base, counter.lower())
@@ -817,12 +829,33 @@ def peer_enable_verified(op, xd, dist):
                    "all-reduce; 16 KB of epoch-stamped words read per rank"}
 
 
+def dump_outputs(out_dir, y, rank, world, limit_bytes=64 << 20):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, the y of that matvec (this
+    rank's rows), as float64 in out_dir/y.npy (N > 1: y_rank<r>.npy).  All ranks together write at most
+    limit_bytes: a longer y is cut to a fixed sample of its entries (sorted indices from numpy PCG64 seed 906),
+    the same in every run.  The inputs are seeded, so two runs see the same x; their y agree to fp64 rounding
+    (about 1e-15 relative), not bit for bit: the default spread sums with fp64 LDS atomics, whose order varies."""
+    os.makedirs(out_dir, exist_ok=True)
+    arr = y.detach().cpu().numpy().astype(np.float64, copy=False)
+    keep = limit_bytes // world // 8
+    if arr.size > keep:
+        arr = arr[np.sort(np.random.default_rng(906).choice(arr.size, size=keep, replace=False))]
+    np.save(os.path.join(out_dir, "y.npy" if world == 1 else f"y_rank{rank}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (one process each); without a launcher N > 1 ranks are spawned here (default 1)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the solver and loss legs, the per-kernel "
+                         "roofline (instrumented repeat, PMC passes), configs B and E, the CPU baseline and, N > 1, "
+                         "the other partition and the all-reduce comparison (the --no-* switches trim these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the y of the last timed matvec to DIR/y.npy (N > 1: each "
+                         "rank's rows to DIR/y_rank<r>.npy), float64; more than 64 MB in all: a fixed seeded sample")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--d", type=int, default=32)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -857,6 +890,8 @@ def main():
         cpu_baseline_child(args.n, args.d, args.cpu_oracle_so, threads_list)
         return
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.kernel_only:
         kernel_only(args.n, args.d, args.kernel_only_nys, args.kernel_only_precision)
         return
@@ -955,8 +990,10 @@ def main():
     # pre-warm, the W warmup and the K timed steps follow.
     pcg = {}
     pcie_rate = None
-    prewarm()
-    if world == 1:
+    full = args.full
+    if full:
+        prewarm()
+    if world == 1 and full:
         # host-pointer calls (the reference's calling convention): x and y staged over PCIe each call
         xh = np.ascontiguousarray(x_host)
         yh = np.zeros(n)
@@ -966,7 +1003,7 @@ def main():
         for _ in range(reps_h):
             op.matsymv(xh, 1.0, 0.0, yh)
         pcie_rate = reps_h / (time.perf_counter() - t0)
-    if world == 1 and not args.no_pcg:
+    if world == 1 and full and not args.no_pcg:
         pcg.update(run_loss(op, torch, n, d, X))
         pcg.update(run_loss(op, torch, n, d, X, ortho=2))
         pcg.update(run_fgmres(op, torch, n))
@@ -1051,12 +1088,14 @@ def main():
     # every kernel (about 13 us per matvec of event overhead, reported as ms_per_step_instrumented) for the
     # per-kernel durations of the roofline
     elapsed, _ = timed(False)
-    elapsed_inst, kern_avg = timed(True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, yd, rank, world)
+    elapsed_inst, kern_avg = timed(True) if full else (None, None)
     if peer is not None and peer.get("verified"):
         op.check()  # a peer wait that gave up in the timed steps fails the bench (raises), loudly
-    per_rank = rank_times(kern_avg, elapsed_inst) if world > 1 else None
+    per_rank = rank_times(kern_avg, elapsed_inst) if world > 1 and full else None
     rows_allreduce = None
-    if peer is not None and peer.get("verified"):
+    if full and peer is not None and peer.get("verified"):
         # the same steps over the communicator's all-reduce, for comparison
         op.disable_peer()
         prewarm()
@@ -1070,7 +1109,7 @@ def main():
         # norms, Hessenberg columns: PeerComm, dist.hip) go through the peer buffers
         peer["solvers"] = bool(peer_enable_verified(op, xd, dist).get("verified"))
     alt = None
-    if world > 1:
+    if world > 1 and full:
         # the other split, timed the same way (W warmup + K steps between barriers, max over ranks)
         other = "components" if args.partition == "rows" else "rows"
         op2 = DistributedAdditiveKernel(X, win, d, 1, comm, partition=other)
@@ -1116,7 +1155,7 @@ def main():
                    "n": n, "d": d, "nwindows": d, "setup_s": setup_s,
                    "parallelism": f"{args.partition}{world}" if world > 1 else "single"},
     }
-    if world == 1:
+    if world == 1 and full:
         result.update(pcg)
         # per-kernel durations: dispatch-attached hipEvents over the instrumented repeat of the timed region
         # (the same begin / end timestamps rocprofv3's kernel trace reports; profiles/ holds that trace of
@@ -1184,14 +1223,15 @@ def main():
                                             "RCCL (library-owned ncclComm, all-reduce enqueued by dist.hip)"
                                             if comm_kind == "rccl" else
                                             "RCCL through torch.distributed (callback fallback, synchronising)")
-        if not args.no_pcg:
+        if full and not args.no_pcg:
             result.update(run_pcg_single(op, torch, n, rows=(rb, re), dist=dist))
             result["pcg_impl"] = f"Nfft4GPSolverPcg on Nfft4GPAmdDistMatSymv ({args.partition}), device-controlled"
             result.update(run_fgmres(op, torch, n, rows=(rb, re), dist=dist))
             result.update(run_fgmres(op, torch, n, rows=(rb, re), dist=dist, ortho=1))
             result.update(run_fgmres(op, torch, n, rows=(rb, re), dist=dist, ortho=2))
             result.update(run_loss(op, torch, n, d, X, rows=(rb, re), dist=dist))
-        result["partition_" + alt["partition"]] = alt
+        if alt is not None:
+            result["partition_" + alt["partition"]] = alt
         if peer is not None:
             result["grid_exchange"] = "peer memory" if peer.get("verified") else "all-reduce"
             result["peer_exchange"] = peer

@@ -63,6 +63,27 @@ def test_failing_rank_fails_the_command(tmp_path):
     assert "rank 1 exited" in r.stderr
 
 
+def test_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: the whole y as float64 when it fits the byte limit; above it the same seeded sample of its
+    entries every time, each rank within its share of the limit."""
+    import numpy as np
+    import torch
+    y = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), y, 0, 1)
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y.numpy())
+    for name in ("b", "c"):  # 2 ranks share 1600 bytes: 100 entries each
+        bench.dump_outputs(str(tmp_path / name), y, 1, 2, limit_bytes=1600)
+    b, c = (np.load(tmp_path / name / "y_rank1.npy") for name in ("b", "c"))
+    assert b.dtype == np.float64 and b.shape == (100,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and set(b) <= set(y.numpy())  # distinct entries of y, in y's order
+
+
+def test_steps_must_be_positive(tmp_path):
+    r = _run(tmp_path, ["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_launcher_world_mismatch_is_refused(tmp_path):
     r = _run(tmp_path, ["--gpus", "4", "--launcher-selftest"], {"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0 and "must agree" in r.stderr

@@ -51,7 +51,8 @@ def main():
         dropped += [c for c in counters if c not in use]
         if not use:
             continue
-        d_out = os.path.join(ROOT, "gpurun_out", "pmc_sq", f"pass{i}")
+        d_out = os.path.join(os.path.abspath(os.environ.get("NFFT4GP_OUT") or os.path.join(ROOT, "bench_out")),
+                             "pmc_sq", f"pass{i}")
         shutil.rmtree(d_out, ignore_errors=True)
         cmd = ["rocprofv3", "--pmc", *use, "--output-format", "csv", "-d", d_out, "-o", "pmc", "--",
                sys.executable, os.path.join(ROOT, "bench.py"), "--kernel-only", "--n", str(args.n), "--d",

@@ -693,6 +693,176 @@ int Nfft4GPAmdAfnShardInfo(void *dafn, int *m1, int *m2, long long *k12_doubles,
 int Nfft4GPAmdDistAfnSolve(void *dafn, int n, NFFT4GP_DOUBLE *x, NFFT4GP_DOUBLE *rhs);
 void Nfft4GPAmdDistAfnFree(void *dafn);
 
+/* ---- training loop under the reference's names (SRC/optimizer/optimizer.h, adam.h, gp_problem.h) ------
+ * The sequence of the reference's training drivers (TESTS/TEST4/foo.cpp:268-347): Nfft4GPGPProblemCreate /
+ * Nfft4GPGpProblemSetup, Nfft4GPOptimizationAdam*, then predict.  Host code; the loss the optimiser steps on
+ * is Nfft4GPGpProblemLoss, which forwards to this library's Nfft4GPGpLoss.  Callers read _nits, _x_history
+ * and _loss_history from the optimiser directly (TEST4/foo.cpp:351-360, :427-430): both structs keep the
+ * reference's field order (offsets tested in tests/test_train_host.py). */
+/* SRC/solvers/solvers.h:36 */
+typedef int (*func_matvec)(void *matrix, char trans, int m, int n, NFFT4GP_DOUBLE alpha, NFFT4GP_DOUBLE *x,
+                           NFFT4GP_DOUBLE beta, NFFT4GP_DOUBLE *y);
+/* SRC/optimizer/optimizer.h:19-23 */
+typedef enum
+{
+   NFFT4GP_OPTIMIZER_UNDEFINED = 0,
+   NFFT4GP_OPTIMIZER_ADAM,
+   NFFT4GP_OPTIMIZER_NLTGCR
+} nfft4gp_optimizer_type;
+/* SRC/optimizer/optimizer.h:35: loss (lossp) and gradient (dloss) at x; either output may be NULL */
+typedef int (*func_loss)(void *problem, NFFT4GP_DOUBLE *x, NFFT4GP_DOUBLE *lossp, NFFT4GP_DOUBLE *dloss);
+/* SRC/optimizer/optimizer.h:43 */
+typedef int (*func_optimization_step)(void *optimizer);
+
+/* SRC/optimizer/adam.h:16-42.  The four histories hold _maxits + 1 entries (of _n values for _x_history and
+ * _grad_history); entry 0 is the starting point. */
+typedef struct NFFT4GP_OPTIMIZER_ADAM_STRUCT
+{
+   int _maxits;
+   NFFT4GP_DOUBLE _tol;
+   func_loss _floss;
+   void *_fdata;
+   int _n;
+   NFFT4GP_DOUBLE _beta1;
+   NFFT4GP_DOUBLE _beta2;
+   NFFT4GP_DOUBLE _epsilon;
+   NFFT4GP_DOUBLE _alpha;
+   NFFT4GP_DOUBLE *_m;
+   NFFT4GP_DOUBLE *_v;
+   NFFT4GP_DOUBLE *_m_hat;
+   NFFT4GP_DOUBLE *_v_hat;
+   int _nits;
+   NFFT4GP_DOUBLE *_loss_history;
+   NFFT4GP_DOUBLE *_x_history;
+   NFFT4GP_DOUBLE *_grad_history;
+   NFFT4GP_DOUBLE *_grad_norm_history;
+} optimizer_adam, *poptimizer_adam;
+
+/* SRC/optimizer/adam.h:50 (defaults adam.c:9-30: maxits 1000, tol 1e-6, beta 0.9 / 0.999, epsilon 1e-8,
+ * learning rate 0.001) */
+void *Nfft4GPOptimizationAdamCreate(void);
+/* SRC/optimizer/adam.h:58 */
+void Nfft4GPOptimizationAdamFree(void *optimizer);
+/* SRC/optimizer/adam.h:69-73 */
+int Nfft4GPOptimizationAdamSetProblem(void *optimizer, func_loss floss, void *fdata, int n);
+/* SRC/optimizer/adam.h:87-94; -1 after the first step */
+int Nfft4GPOptimizationAdamSetOptions(void *optimizer, int maxits, NFFT4GP_DOUBLE tol, NFFT4GP_DOUBLE beta1,
+                                      NFFT4GP_DOUBLE beta2, NFFT4GP_DOUBLE epsilon, NFFT4GP_DOUBLE alpha);
+/* SRC/optimizer/adam.h:103: allocates the moments and histories, copies x (n values) to entry 0 and prints
+ * the banner; -1 after the first step */
+int Nfft4GPOptimizationAdamInit(void *optimizer, NFFT4GP_DOUBLE *x);
+/* SRC/optimizer/adam.h:111 (a func_optimization_step): 0 continue, 1 _maxits reached, 2 gradient norm below
+ * _tol, -1 the loss failed (_nits is not incremented then).  The per-step line is the reference's
+ * (adam.c:173-176), except that it prints min(_n, 3) parameters: the reference prints three whatever _n is
+ * and reads past the history when _n < 3. */
+int Nfft4GPOptimizationAdamStep(void *optimizer);
+
+/* SRC/optimizer/gp_problem.h:20-74.  The struct owns none of the arrays it points at, except _dwork. */
+typedef struct NFFT4GP_GP_OPTIMIZER_STRUCT
+{
+   nfft4gp_optimizer_type _type;
+   func_optimization_step _fstep;
+   void *_optimizer;
+   NFFT4GP_DOUBLE *_dwork;
+   NFFT4GP_DOUBLE *_data_train;
+   int _data_train_n;
+   int _data_train_ldim;
+   int _data_train_d;
+   NFFT4GP_DOUBLE *_label_train;
+   func_kernel _fkernel;
+   void *_vfkernel_data;
+   func_free _kernel_data_free;
+   func_symmatvec _matvec;
+   func_symmatvec _dmatvec;
+   func_kernel _precond_fkernel;
+   void *_precond_vfkernel_data;
+   func_free _precond_kernel_data_free;
+   precond_kernel_setup _precond_setup;
+   func_solve _precond_solve;
+   func_trace _precond_trace;
+   func_logdet _precond_logdet;
+   func_dvp _precond_dvp;
+   func_free _precond_reset;
+   void *_precond_data;
+   int _atol_loss;
+   NFFT4GP_DOUBLE _tol_loss;
+   int _wsize_loss;
+   int _maxits_loss;
+   int _nvecs_loss;
+   NFFT4GP_DOUBLE *_radamacher_loss;
+   nfft4gp_transform_type _transform;
+   int *_mask;
+   int _print_level_loss;
+   NFFT4GP_DOUBLE *_data_predict;
+   int _data_predict_n;
+   int _data_predict_ldim;
+   int _data_predict_d;
+   NFFT4GP_DOUBLE *_label_predict;
+   func_matvec _matvec_predict;
+   int _atol_predict;
+   NFFT4GP_DOUBLE _tol_predict;
+   int _wsize_predict;
+   int _maxits_predict;
+   int _print_level_predict;
+   int _retuire_std;
+} nfft4gp_gp_problem, *pnfft4gp_gp_problem;
+
+/* SRC/optimizer/gp_problem.h:82 (defaults gp_problem.c:15-58) */
+void *Nfft4GPGPProblemCreate(void);
+/* SRC/optimizer/gp_problem.h:90 */
+void Nfft4GPGPProblemFree(void *gp_problem);
+/* SRC/optimizer/gp_problem.h:142-188: stores every argument in its field (retuire_std too; gp_problem.c:75-175
+ * leaves that one field unset) */
+int Nfft4GPGpProblemSetup(void *gp_problem, nfft4gp_optimizer_type type, func_optimization_step fstep, void *optimizer,
+                          NFFT4GP_DOUBLE *data_train, int data_train_n, int data_train_ldim, int data_train_d,
+                          NFFT4GP_DOUBLE *label_train, func_kernel fkernel, void *vfkernel_data,
+                          func_free kernel_data_free, func_symmatvec matvec, func_symmatvec dmatvec,
+                          func_kernel precond_fkernel, void *precond_vfkernel_data,
+                          func_free precond_kernel_data_free, precond_kernel_setup precond_setup,
+                          func_solve precond_solve, func_trace precond_trace, func_logdet precond_logdet,
+                          func_dvp precond_dvp, func_free precond_reset, void *precond_data, int atol_loss,
+                          NFFT4GP_DOUBLE tol_loss, int wsize_loss, int maxits_loss, int nvecs_loss,
+                          NFFT4GP_DOUBLE *radamacher_loss, nfft4gp_transform_type transform, int *mask,
+                          int print_level_loss, NFFT4GP_DOUBLE *data_predict, int data_predict_n,
+                          int data_predict_ldim, int data_predict_d, NFFT4GP_DOUBLE *label_predict,
+                          func_matvec matvec_predict, int atol_predict, NFFT4GP_DOUBLE tol_predict, int wsize_predict,
+                          int maxits_predict, int print_level_predict, int retuire_std);
+/* SRC/optimizer/gp_problem.h:199 (a func_loss): Nfft4GPGpLoss on the problem's training fields */
+int Nfft4GPGpProblemLoss(void *problem, NFFT4GP_DOUBLE *x, NFFT4GP_DOUBLE *lossp, NFFT4GP_DOUBLE *dloss);
+
+/* ---- fitted model: the posterior mean at new points without the training data -----------
+ * After the spread and grid steps of a matvec with alpha = (K + mu I)^{-1} y, the handle's table of
+ * interpolation polynomials (nw x 64 cells x 8 coefficients) evaluated at ANY point of the handle's domain
+ * gives f^2 (1/nw) sum_c K_c(x*, X) alpha, the posterior mean.  A model keeps that table (128 KB at 32
+ * windows) plus each window's feature index, centre and scale; predicting reads the new points once and needs
+ * no layout, no solve and no training point.  1-D windows only.
+ * Nfft4GPAmdModelCreate: additive_handle a whole (one GPU, not a row or component shard, not a distributed
+ * operator) additive handle of this library after a Gaussian / Matern-1/2 setup call, every window of exactly
+ * one feature, n its number of points; alpha (n, host or device).  Runs the handle's spread and grid steps on
+ * the library stream and copies the table; the handle may be freed afterwards and its matvecs are unaffected.
+ * Works in both precision modes (Nfft4GPAmdSetPrecision).  NULL (message on stderr) otherwise. */
+void *Nfft4GPAmdModelCreate(void *additive_handle, const NFFT4GP_DOUBLE *alpha, int n);
+/* mean[i] = f^2 sum_c Horner(H[c][cell_c], s_c) for the n_new rows of Xnew (column-major, leading dimension
+ * ldim >= n_new, d columns: the model's d, else -1), windows added in the order c = 0 .. nw - 1 with no atomics:
+ * bitwise reproducible and independent of how the points are batched.  Xnew, mean: host or device.  Per
+ * window xs = (x - centre_c) scale_c is quantised exactly as the setup does, so a training point lands on its
+ * own cell and offset.  A point with |xs| > 0.25 + 2^-33 in any window (outside the radius the training points
+ * were scaled to: the regularised kernel is the kernel only up to distance 1/2) or a non-finite coordinate
+ * gets NaN and is counted in *n_outside (may be NULL); the call still returns 0. */
+int Nfft4GPAmdModelPredict(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, NFFT4GP_DOUBLE *mean,
+                           long long *n_outside);
+/* nw, d, kernel (0 Gaussian, 1 Matern-1/2) and hyper3 = (f, l, mu); any output may be NULL */
+int Nfft4GPAmdModelInfo(void *model, int *nw, int *d, int *kernel, NFFT4GP_DOUBLE *hyper3);
+/* the model's arrays to the host: H (nw * 64 * 8, [window][cell][degree], polynomials in s = 2^32 x the offset
+ * from the cell's middle), centre, scale, feature (nw each); any output may be NULL */
+int Nfft4GPAmdModelCoefficients(void *model, NFFT4GP_DOUBLE *H, NFFT4GP_DOUBLE *centre, NFFT4GP_DOUBLE *scale,
+                                int *feature);
+/* a model from those arrays (host): the load half of save / load */
+void *Nfft4GPAmdModelFromCoefficients(int nw, int d, int kernel, const NFFT4GP_DOUBLE *hyper3,
+                                      const NFFT4GP_DOUBLE *H, const NFFT4GP_DOUBLE *centre,
+                                      const NFFT4GP_DOUBLE *scale, const int *feature);
+void Nfft4GPAmdModelFree(void *model);
+
 /* ---- host-only helpers (no GPU needed): the setup math of the device plan, exported so the CPU
  * test-suite can check it and emulate the kernels against the oracle ------------------------------- */
 /* tap polynomial coefficients C[t*NC + d], t = 0..9, d = 0..NC-1 (monomials in u = frac - 1/2);

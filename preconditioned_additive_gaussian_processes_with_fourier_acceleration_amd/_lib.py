@@ -45,6 +45,56 @@ class NfftKernelStruct(C.Structure):
     ]
 
 
+LOSS = C.CFUNCTYPE(C.c_int, vp, dp, dp, dp)  # func_loss (SRC/optimizer/optimizer.h:35)
+
+
+class OptimizerAdamStruct(C.Structure):
+    """optimizer_adam, field layout of SRC/optimizer/adam.h:16-42."""
+    _fields_ = [
+        ("_maxits", C.c_int),
+        ("_tol", C.c_double),
+        ("_floss", vp),
+        ("_fdata", vp),
+        ("_n", C.c_int),
+        ("_beta1", C.c_double),
+        ("_beta2", C.c_double),
+        ("_epsilon", C.c_double),
+        ("_alpha", C.c_double),
+        ("_m", dp),
+        ("_v", dp),
+        ("_m_hat", dp),
+        ("_v_hat", dp),
+        ("_nits", C.c_int),
+        ("_loss_history", dp),
+        ("_x_history", dp),
+        ("_grad_history", dp),
+        ("_grad_norm_history", dp),
+    ]
+
+
+# nfft4gp_gp_problem (SRC/optimizer/gp_problem.h:20-74): its fields after _dwork are Nfft4GPGpProblemSetup's
+# arguments after the problem, in order; (name, ctypes type)
+GP_PROBLEM_FIELDS = [
+    ("_type", C.c_int), ("_fstep", vp), ("_optimizer", vp), ("_dwork", vp),
+    ("_data_train", vp), ("_data_train_n", C.c_int), ("_data_train_ldim", C.c_int), ("_data_train_d", C.c_int),
+    ("_label_train", vp), ("_fkernel", vp), ("_vfkernel_data", vp), ("_kernel_data_free", vp), ("_matvec", vp),
+    ("_dmatvec", vp), ("_precond_fkernel", vp), ("_precond_vfkernel_data", vp), ("_precond_kernel_data_free", vp),
+    ("_precond_setup", vp), ("_precond_solve", vp), ("_precond_trace", vp), ("_precond_logdet", vp),
+    ("_precond_dvp", vp), ("_precond_reset", vp), ("_precond_data", vp), ("_atol_loss", C.c_int),
+    ("_tol_loss", C.c_double), ("_wsize_loss", C.c_int), ("_maxits_loss", C.c_int), ("_nvecs_loss", C.c_int),
+    ("_radamacher_loss", vp), ("_transform", C.c_int), ("_mask", vp), ("_print_level_loss", C.c_int),
+    ("_data_predict", vp), ("_data_predict_n", C.c_int), ("_data_predict_ldim", C.c_int),
+    ("_data_predict_d", C.c_int), ("_label_predict", vp), ("_matvec_predict", vp), ("_atol_predict", C.c_int),
+    ("_tol_predict", C.c_double), ("_wsize_predict", C.c_int), ("_maxits_predict", C.c_int),
+    ("_print_level_predict", C.c_int), ("_retuire_std", C.c_int),
+]
+
+
+class GpProblemStruct(C.Structure):
+    """nfft4gp_gp_problem, field layout of SRC/optimizer/gp_problem.h:20-74."""
+    _fields_ = GP_PROBLEM_FIELDS
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "Nfft4GPKernelParamCreate": (vp, [C.c_int, C.c_int]),
@@ -202,6 +252,24 @@ _SIGS = {
     "Nfft4GPAmdDistAfnFree": (None, [vp]),
     "Nfft4GPAmdDistNysSolve": (C.c_int, [vp, C.c_int, vp, vp]),
     "Nfft4GPAmdDistNysFree": (None, [vp]),
+    "Nfft4GPOptimizationAdamCreate": (vp, []),
+    "Nfft4GPOptimizationAdamFree": (None, [vp]),
+    "Nfft4GPOptimizationAdamSetProblem": (C.c_int, [vp, vp, vp, C.c_int]),
+    "Nfft4GPOptimizationAdamSetOptions": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                    C.c_double]),
+    "Nfft4GPOptimizationAdamInit": (C.c_int, [vp, vp]),
+    "Nfft4GPOptimizationAdamStep": (C.c_int, [vp]),
+    "Nfft4GPGPProblemCreate": (vp, []),
+    "Nfft4GPGPProblemFree": (None, [vp]),
+    # the problem, then the struct's fields from _data_train on, preceded by type, fstep, optimizer
+    "Nfft4GPGpProblemSetup": (C.c_int, [vp] + [t for nm, t in GP_PROBLEM_FIELDS if nm != "_dwork"]),
+    "Nfft4GPGpProblemLoss": (C.c_int, [vp, vp, vp, vp]),
+    "Nfft4GPAmdModelCreate": (vp, [vp, vp, C.c_int]),
+    "Nfft4GPAmdModelPredict": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdModelInfo": (C.c_int, [vp, ip, ip, ip, dp]),
+    "Nfft4GPAmdModelCoefficients": (C.c_int, [vp, vp, vp, vp, vp]),
+    "Nfft4GPAmdModelFromCoefficients": (vp, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "Nfft4GPAmdModelFree": (None, [vp]),
     "Nfft4GPAmdHostTapPoly": (C.c_int, [vp]),
     "Nfft4GPAmdHostCirculant": (C.c_int, [C.c_int, C.c_double, C.c_double, vp, vp]),
     "Nfft4GPAmdHostPrepare": (C.c_double, [vp, C.c_int, vp]),

@@ -201,9 +201,12 @@ struct AdditivePlan {
    int n_global = 0, row_begin = 0, row_end = 0, n = 0;  // n = local rows
    int nw = 0, dw = 0, skip_last = 0;
    std::vector<int> comp_dims;
+   int d = 0;                      // columns of the data the handle was created over
+   std::vector<int> comp_feature;  // each window's first feature (column of the data); -1: an empty window
    // per-component cached first-setup state (nfft_interface.c:150-213)
    bool points_ready = false;
    std::vector<double> comp_scale;
+   std::vector<double> comp_centre;  // 1-D windows: the mean the first setup subtracted (nfft_interface.c:150-160)
    std::vector<double> comp_sigma;
    int kernel = 0;  // 0 gaussian, 1 matern12
    double f = 1.0, l = 1.0, mu = 0.0;
@@ -298,6 +301,8 @@ int additive_matvec_multi(void* str, int nv, double alpha, const double* const* 
 // y = A x (alpha = 1, beta = 0) and *d_dot = (y, x) on device pointers: the matvec + dot of a CG step in
 // the matvec's own three launches (used by Nfft4GPSolverPcg when its operator is this library's)
 int additive_matvec_dot(void* str, const double* d_x, double* d_y, double* d_dot);
+// the plan of this library's additive handle (nfft_api.cpp); NULL when str has none
+AdditivePlan* additive_plan_of(void* str);
 // true when additive_matvec_dot can serve this handle: points set up, whole-row (not a row shard) handle,
 // and a 1-D layout whose block count the fused grid reduction can sum (nblocks <= kRedMaxBlocks)
 bool additive_fused_dot_ok(void* str);

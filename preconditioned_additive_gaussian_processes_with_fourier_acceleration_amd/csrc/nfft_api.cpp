@@ -193,13 +193,15 @@ int upload(T** dptr, const std::vector<T, A>& h)
 
 // nfft_interface.c:150-213: centre by the mean, scale to radius 0.25 unless already in
 // [0.125, 0.25], computed once from all n_global points (same operation order as the reference).
-double centre_and_scale(const double* col, int n_global, int d, std::vector<double>& xs)
+// centre (d entries, may be NULL) receives the means that were subtracted.
+double centre_and_scale(const double* col, int n_global, int d, std::vector<double>& xs, double* centre = nullptr)
 {
    xs.assign(col, col + (size_t)n_global * d);
    for (int i = 0; i < d; i++) {
       double c = 0.0;
       for (int j = 0; j < n_global; j++) c += xs[(size_t)i * n_global + j];
       c /= (double)n_global;
+      if (centre) centre[i] = c;
       for (int j = 0; j < n_global; j++) xs[(size_t)i * n_global + j] -= c;
    }
    double radius = 0.0;
@@ -233,6 +235,7 @@ int plan_build_points(AdditivePlan& P, const double* buffer)
    const int ng = P.n_global;
    RawVec<uint32_t> qc((size_t)P.nw * P.n);  // every entry is written below
    P.comp_scale.assign(P.nw, 1.0);
+   P.comp_centre.assign(P.nw, 0.0);  // 1-D windows only (the fitted model, model.hip)
    std::vector<double> xs;
    if (std::any_of(P.comp_dims.begin(), P.comp_dims.end(), [](int d) { return d != 1; })) {
       // windows of several features: 64^d grids (nfft_md.hip)
@@ -257,7 +260,7 @@ int plan_build_points(AdditivePlan& P, const double* buffer)
       std::vector<double> xw;
       for (int c = next++; c < P.nw; c = next++) {
          const double* col = buffer + (size_t)c * ng * P.dw;  // nfft_interface.c:703 stride n*dwindows
-         P.comp_scale[c] = centre_and_scale(col, ng, 1, xw);
+         P.comp_scale[c] = centre_and_scale(col, ng, 1, xw, &P.comp_centre[c]);
          if (P.comp_scale[c] < 0.0) continue;
          for (int j = 0; j < P.n; j++) qc[(size_t)c * P.n + j] = quantize(xw[(size_t)P.row_begin + j]);
       }
@@ -547,7 +550,8 @@ void env_layout(AdditivePlan& P)
    if (const char* e = getenv("NFFT4GP_AMD_PRECISION")) P.rec = atoi(e) == 32 ? 4 : 5;
 }
 
-void* additive_create(double* data, int n_global, int ldim, int* windows, int nwindows, int dwindows, int rb, int re)
+void* additive_create(double* data, int n_global, int ldim, int d, int* windows, int nwindows, int dwindows, int rb,
+                      int re)
 {
    nfft4gp_kernel* kd = kernel_struct_create(3 * n_global);  // nfft_interface.c:624
    kd->_iparams[0] = nwindows;
@@ -570,6 +574,7 @@ void* additive_create(double* data, int n_global, int ldim, int* windows, int nw
    P.n = re - rb;
    P.nw = nwindows;
    P.dw = dwindows;
+   P.d = d;
    P.skip_last = kd->_iparams[2];
    P.weight = 1.0 / (double)nwindows;  // nfft_interface.c:806
    env_layout(P);
@@ -580,11 +585,13 @@ void* additive_create(double* data, int n_global, int ldim, int* windows, int nw
       for (int j = 0; j < dwindows; j++) {
          if (fw[0] >= 0) {
             memcpy(dst, data + (size_t)fw[0] * ldim, sizeof(double) * n_global);
+            if (actual == 0) P.comp_feature.push_back(fw[0]);
             fw++;
             dst += n_global;
             actual++;
          }
       }
+      if (actual == 0) P.comp_feature.push_back(-1);
       P.comp_dims.push_back(actual);
    }
    kd->_external = E;
@@ -653,6 +660,12 @@ int additive_matvec_chunked(void* str, double alpha, const double* d_x, double* 
       if (done(ctx, (size_t)b0 * P.B, std::min((size_t)b1 * P.B, (size_t)P.n))) return -1;
    }
    return 0;
+}
+
+AdditivePlan* additive_plan_of(void* str)
+{
+   PlanExt* E = additive_plan(str);
+   return E ? &E->P : nullptr;
 }
 
 // rows of an additive handle: local (this shard) and global; -1 when str is not an additive handle
@@ -810,20 +823,18 @@ void Nfft4GPKernelParamFree(void* str)
 void* Nfft4GPNFFTAdditiveKernelParamCreate(double* data, int n, int ldim, int d, int* windows, int nwindows,
                                            int dwindows)
 {
-   (void)d;
    RandScope rand_scope;  // HIP's first use may draw rand(); the reference's NFFT entry points draw none
-   return additive_create(data, n, ldim, windows, nwindows, dwindows, 0, n);
+   return additive_create(data, n, ldim, d, windows, nwindows, dwindows, 0, n);
 }
 
 void* Nfft4GPAmdAdditiveShardCreate(double* data, int n_global, int ldim, int d, int* windows, int nwindows,
                                     int dwindows, int row_begin, int row_end)
 {
-   (void)d;
    if (row_begin < 0 || row_end > n_global || row_begin > row_end) {
       fprintf(stderr, "nfft4gp_amd: invalid shard rows [%d, %d) of %d\n", row_begin, row_end, n_global);
       return NULL;
    }
-   return additive_create(data, n_global, ldim, windows, nwindows, dwindows, row_begin, row_end);
+   return additive_create(data, n_global, ldim, d, windows, nwindows, dwindows, row_begin, row_end);
 }
 
 int Nfft4GPNFFTAdditiveKernelGaussianKernel(void* str, double* data, int n, int ldim, int d, int* permr, int kr,

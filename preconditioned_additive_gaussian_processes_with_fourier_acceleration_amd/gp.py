@@ -7,6 +7,10 @@
                 Nfft4GPAmdDistMatSymv / Nfft4GPAmdDistGradMatSymv (BASELINE configs[4]).
 ``gp_predict``  Nfft4GPAdditiveNFFTGpPredict (SRC/external/nfft_interface.c:873-1068): posterior mean and,
                 optionally, standard deviation at new points (a second handle over [X; Xp], as TEST4 does).
+``gp_fit``      the reference's training sequence (TESTS/TEST4/foo.cpp:268-347): Nfft4GPGpProblemSetup, then
+                Nfft4GPOptimizationAdam* stepping on Nfft4GPGpProblemLoss.
+``gp_model``    solve (K + mu I) alpha = y once and keep the result as a model.FittedModel, which predicts new
+                points without the training data.
 """
 from __future__ import annotations
 
@@ -15,7 +19,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .nfft import NFFTAdditiveKernel
+from .model import FittedModel
+from .nfft import GAUSSIAN, NFFTAdditiveKernel
 
 _vp = C.c_void_p
 _GPLOSS_ARGS = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -109,3 +114,113 @@ def gp_predict(X, Xp, windows, nwindows, dwindows, y, hyper, maxits=100, tol=1e-
     if rc:
         raise RuntimeError("Nfft4GPAdditiveNFFTGpPredict failed")
     return mean, (std if with_std else None)
+
+
+def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, tol=1e-3,
+           op=None, **loss_kwargs):
+    """Adam on the GP loss, run by the library: Nfft4GPGpProblemSetup carries gp_loss's arguments,
+    Nfft4GPOptimizationAdamStep calls Nfft4GPGpProblemLoss and updates the hyperparameters (``hyper0`` = (f, l, mu)
+    before the transform), for at most ``steps`` steps or until the gradient norm falls below ``tol``.
+    ``loss_kwargs`` are gp_loss's: maxits, nvecs, rademacher, transform, mask, print_level (and loss_tol, its tol).
+    Returns (hyper_history [nits + 1, 3], loss_history [nits], grad_norm_history [nits], flag): entry k of the
+    loss and gradient-norm histories belongs to hyper_history[k]; flag is the last step's status (1 steps
+    reached, 2 gradient norm below tol, -1 the loss failed).  The library prints one line per step, as the
+    reference does."""
+    unknown = set(loss_kwargs) - {"maxits", "nvecs", "rademacher", "transform", "mask", "print_level", "loss_tol"}
+    if unknown:
+        raise TypeError(f"unknown loss arguments: {sorted(unknown)}")
+    maxits = int(loss_kwargs.get("maxits", 50))
+    nvecs = int(loss_kwargs.get("nvecs", 10))
+    rademacher = loss_kwargs.get("rademacher")
+    transform = int(loss_kwargs.get("transform", 0))
+    mask = loss_kwargs.get("mask")
+    print_level = int(loss_kwargs.get("print_level", -1))
+    loss_tol = float(loss_kwargs.get("loss_tol", 1e-6))
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be at least 1")
+    X = np.asarray(X, dtype=np.float64)
+    if op is None:
+        X = np.asfortranarray(X)  # a given op holds its own points (gp_loss)
+        op = NFFTAdditiveKernel(X, windows, nwindows, dwindows)
+    elif not isinstance(op, NFFTAdditiveKernel):
+        raise TypeError("gp_fit runs on an NFFTAdditiveKernel")
+    n, d = X.shape
+    if op.n != n:
+        raise ValueError("op was created over a different number of points")
+    if len(y) != n:
+        raise ValueError(f"{len(y)} labels for {n} rows")
+    lab = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    x0 = np.ascontiguousarray(np.asarray(hyper0, dtype=np.float64))
+    if x0.size != 3:
+        raise ValueError("hyper0 = (f, l, mu)")
+    if rademacher is None:
+        R, r_ptr = None, None
+    elif hasattr(rademacher, "data_ptr"):
+        R, r_ptr = rademacher, rademacher.data_ptr()
+    else:
+        R = np.asfortranarray(np.asarray(rademacher, dtype=np.float64))
+        r_ptr = R.ctypes.data
+    m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
+    L = _lib.lib()
+    adam = L.Nfft4GPOptimizationAdamCreate()
+    prob = L.Nfft4GPGPProblemCreate()
+    try:
+        rc = L.Nfft4GPGpProblemSetup(
+            prob, 1, _lib.fnptr("Nfft4GPOptimizationAdamStep"), adam,  # NFFT4GP_OPTIMIZER_ADAM
+            X.ctypes.data, n, n, d, lab.ctypes.data,
+            _lib.fnptr("Nfft4GPNFFTAdditiveKernelGaussianKernel"), op.h, None,
+            _lib.fnptr("Nfft4GPAdditiveNFFTMatSymv"), _lib.fnptr("Nfft4GPAdditiveNFFTGradMatSymv"),
+            None, None, None, None, None, None, None, None, None, None,  # no preconditioner
+            0, loss_tol, maxits, maxits, nvecs, r_ptr, transform, m.ctypes.data if m is not None else None,
+            print_level,
+            None, 0, 0, 0, None, None, 0, 1e-6, 0, 100, 0, 0)  # the prediction fields are not used here
+        if rc or L.Nfft4GPOptimizationAdamSetProblem(adam, _lib.fnptr("Nfft4GPGpProblemLoss"), prob, 3) or \
+                L.Nfft4GPOptimizationAdamSetOptions(adam, steps, float(tol), float(beta1), float(beta2), float(eps),
+                                                    float(lr)) or \
+                L.Nfft4GPOptimizationAdamInit(adam, x0.ctypes.data):
+            raise RuntimeError("the optimiser setup failed")
+        flag = 0
+        while flag == 0:
+            flag = L.Nfft4GPOptimizationAdamStep(adam)
+        st = _lib.OptimizerAdamStruct.from_address(adam)
+        nits = st._nits
+        hyper = np.ctypeslib.as_array(st._x_history, shape=(nits + 1, 3)).copy()
+        loss = np.ctypeslib.as_array(st._loss_history, shape=(steps + 1,))[:nits].copy()
+        gnorm = np.ctypeslib.as_array(st._grad_norm_history, shape=(steps + 1,))[:nits].copy()
+    finally:
+        L.Nfft4GPOptimizationAdamFree(adam)
+        L.Nfft4GPGPProblemFree(prob)
+    del R
+    return hyper, loss, gnorm, int(flag)
+
+
+def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None):
+    """The fitted model at the hyperparameters ``hyper`` = (f, l, mu) before the transform: sets the kernel up
+    (Gaussian, or the kernel ``op`` was last set up with), solves f^2 (K + mu I) alpha = y with FGMRES on the
+    device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse."""
+    import torch
+
+    from .solvers import fgmres
+    X = np.asarray(X, dtype=np.float64)
+    kernel = GAUSSIAN
+    if op is None:
+        op = NFFTAdditiveKernel(np.asfortranarray(X), windows, nwindows, dwindows)
+    elif not isinstance(op, NFFTAdditiveKernel):
+        raise TypeError("gp_model runs on an NFFTAdditiveKernel")
+    elif op._kernel is not None:
+        kernel = op._kernel
+    if op.n != X.shape[0] or len(y) != op.n:
+        raise ValueError("X, y and op must have the same number of points")
+    L = _lib.lib()
+    t, dt = C.c_double(), C.c_double()
+    flm = []
+    for v in np.asarray(hyper, dtype=np.float64).ravel()[:3]:
+        if L.Nfft4GPTransform(int(transform), float(v), 0, C.byref(t), C.byref(dt)) != 0:
+            raise RuntimeError("Nfft4GPTransform failed")
+        flm.append(t.value)
+    if op.setup(kernel, f=flm[0], l=flm[1], mu=flm[2]) != 0:
+        raise RuntimeError("the kernel setup failed")
+    b = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float64)), device="cuda")
+    alpha = fgmres(op, b, kdim=int(maxits), maxits=int(maxits), tol=float(tol))[0]
+    return FittedModel.from_operator(op, alpha)

@@ -218,6 +218,9 @@ struct AdditivePlan {
    // -1 (auto): 0 or 3 by the layout's size; 0: the spread; 1: the same with timeline stamps; 2: round-4 moment
    // table (A/B); 3: the next tile loaded before the current one's moments
    int spread_variant = -1;
+   // the spread's fold of the moments into grid values: 1 = on the matrix unit (fold_window_mfma, nfft_kernels.hip),
+   // 0 = the chain of 80 FMAs per grid value (A/B; also what a block too small for the fold's rows 8-9 runs)
+   int spread_fold = 1;
    // deterministic 1-D matvec: the spread's moment flushes and the interpolation's y adds are rounded to a grid on
    // which every sum is exact, so results do not depend on the order of the LDS atomics (Nfft4GPAmdSetDeterministic)
    bool det = false;

@@ -546,6 +546,7 @@ void env_layout(AdditivePlan& P)
       if (v >= 1 && v <= 64) P.CG = v;
    }
    if (const char* e = getenv("NFFT4GP_AMD_SPREAD_VARIANT")) P.spread_variant = atoi(e);
+   if (const char* e = getenv("NFFT4GP_AMD_SPREAD_FOLD")) P.spread_fold = atoi(e) != 0;
    if (const char* e = getenv("NFFT4GP_AMD_DET")) P.det = atoi(e) != 0;
    if (const char* e = getenv("NFFT4GP_AMD_PRECISION")) P.rec = atoi(e) == 32 ? 4 : 5;
 }

@@ -4,9 +4,10 @@
 //   k_spread  one workgroup per (block of B points, group of CG windows).  The workgroup stages the
 //             block's alpha slice (B doubles) in LDS once for its windows (by LDS-DMA,
 //             global_load_lds_dwordx4: no VGPR round trip, 46.7 -> 43.1 us at config C); each lane walks one R-point
-//             run of a single (window, cell), accumulates the kNC = 10 moments alpha*u^d in registers and
+//             run of a single (window, cell), accumulates the kNC = 8 moments alpha*u^d in registers and
 //             flushes them with ds_add_f64 into an LDS moment table; the workgroup finally folds the
-//             moments into 64-cell partial grids (taps = C * M) and writes them to part[comp][block].
+//             moments into 64-cell partial grids (taps = C * M, on the matrix unit: fold_window_mfma) and writes
+//             them to part[comp][block].
 //             HBM: 5 B per (point, window) -- 12-bit local index + 26-bit offset in the cell -- + alpha.
 //   k_grid    one workgroup per window: sum of the partial grids (fixed order, deterministic), the
 //             64x64 real circulant (= FFT . diag(bhat/phihut^2) . IFFT restricted to Re), and the
@@ -210,8 +211,59 @@ __device__ __forceinline__ uint32_t det_interp_exp(const double* __restrict__ hb
    return min(bY + 2u, 2046u);
 }
 
+// The fold of one window on the matrix unit (v_mfma_f64_16x16x4_f64), by one wave: G = C M, a 10 x 8 by 8 x 64
+// product, then g[gi] = sum_t G[t][(gi + m - t) mod 64].  The chain below reads every M[cell][d] ten times (once
+// per tap: 80 ds_read_b64 per grid value); here each operand is read once.  Lane maps as at nystrom.hip's k_gemm_f64:
+//   A[i = lane & 15][k = lane >> 4] = C[i][4 ks + k] (rows 10-15 zero; fold_tap_operand, loaded by the caller before
+//   the run loop's closing barrier so that its latency is spent there), B[k = lane >> 4][j = lane & 15] =
+//   M[d = 4 ks + k][cell = 16 cb + j] (mrow: the window's [degree][cell] rows, MOMT 1), two k-steps x four column
+//   blocks: 8 ds_read_b64 + 8 MFMAs; D[t = (lane >> 4) + 4 reg][cell = 16 cb + (lane & 15)].
+// G's rows 0-7 go in place over the window's moment rows (all eight B values are read first, and after the run
+// loop's barrier only this wave touches them), rows 8-9 into grow89 (128 doubles of the dead alpha slice).  Returns
+// lane gi's grid value; the taps are summed in fixed order, so the result does not depend on anything but M.
+constexpr bool kFoldMfmaOk = kNC == 8 && kTaps <= 12 && kNos == 64;  // two k-steps of 4 degrees, taps in D's rows 0-11
+template <int REC>
+__device__ __forceinline__ void fold_tap_operand(double (&a)[2], int lane)
+{
+   const int i = lane & 15, k = lane >> 4;
+   const double* ct = REC == 4 ? c_taps_u : c_taps;
+#pragma unroll
+   for (int ks = 0; ks < 2; ks++) a[ks] = i < kTaps ? ct[i * kNC + 4 * ks + k] : 0.0;
+}
+__device__ __forceinline__ double fold_window_mfma(const double (&a)[2], double* mrow, double* grow89, int lane)
+{
+   typedef double f64x4 __attribute__((ext_vector_type(4)));
+   const int i = lane & 15, k = lane >> 4;
+   double bm[2][4];
+#pragma unroll
+   for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+      for (int cb = 0; cb < 4; cb++) bm[ks][cb] = mrow[(4 * ks + k) * kNos + 16 * cb + i];
+#pragma unroll
+   for (int cb = 0; cb < 4; cb++) {
+      f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], bm[0][cb], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], bm[1][cb], acc, 0, 0, 0);
+      mrow[k * kNos + 16 * cb + i] = acc[0];        // taps 0-3
+      mrow[(4 + k) * kNos + 16 * cb + i] = acc[1];  // taps 4-7
+      if (k < kTaps - 8) grow89[k * kNos + 16 * cb + i] = acc[2];  // taps 8, 9
+   }
+   // the other lanes' G values, written above, are read below: LDS operations of one wave complete in order
+   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+   __builtin_amdgcn_wave_barrier();
+   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+   double v = 0.0;
+#pragma unroll
+   for (int tp = 0; tp < kTaps; tp++) {
+      const int cell = (lane + kM - tp) & (kNos - 1);
+      v += tp < 8 ? mrow[tp * kNos + cell] : grow89[(tp - 8) * kNos + cell];
+   }
+   return v;
+}
+
 // at most 80 VGPRs, so three 512-thread workgroups (24 waves) share a CU
 // PIPE (variant 3, layouts past the Infinity Cache): the next tile's loads issued before the current tile's moments
+// fold (AdditivePlan::spread_fold): 1 = the windows' folds on the matrix unit (fold_window_mfma), 0 = the chain
 template <int THREADS, bool TIMELINE = false, int MOMT = 1, bool DET = false, int REC = 5, bool PIPE = false>
 __global__ __launch_bounds__(THREADS, 6) void k_spread(const uint16_t* __restrict__ meta,
                                                       const uint32_t* __restrict__ lo,
@@ -219,7 +271,7 @@ __global__ __launch_bounds__(THREADS, 6) void k_spread(const uint16_t* __restric
                                                       const int* __restrict__ tile_off, const int* __restrict__ cmax,
                                                       const double* __restrict__ x, int n, int B, int nblocks,
                                                       int ngroups, int CG, int nw, double* __restrict__ part,
-                                                      double* __restrict__ gsum)
+                                                      double* __restrict__ gsum, int fold)
 {
    extern __shared__ __attribute__((aligned(16))) double smem[];
    const int Bp = B + kPad;
@@ -243,6 +295,9 @@ __global__ __launch_bounds__(THREADS, 6) void k_spread(const uint16_t* __restric
 
    // the first run's loads and the alpha slice are in flight together
    TileRegs cur, nxt;
+   // (the alpha staging issued before the tile_off loads, or between them and the first tile's loads, is no faster:
+   // spread 33.5 / 34.6 us against 32.1 / 34.5 at config C, profiles/spread_fold_ab.txt -- the first tile's loads,
+   // not the slice's, are what the barrier waits for)
    const int t1 = tile_off[b * ngroups + g + 1];
    int t = tile_off[b * ngroups + g] + wave;
    if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
@@ -320,13 +375,26 @@ __global__ __launch_bounds__(THREADS, 6) void k_spread(const uint16_t* __restric
       else if (t + nwaves < t1)
          load_tile<REC>(cur, meta, lo, qarr, t + nwaves, lane);
    }
+   // fold moments into the 64-cell partial grid of every window of this group:
+   //   g[gi] = sum_t sum_d C[t][d] M[(gi + m - t) mod 64][d]
+   // on the matrix unit (MOMT 1): wave w folds windows w, w + nwaves, ... by itself (no further barrier); rows 8-9 of
+   // window cl's G need 128 doubles of the alpha slice, which a forced small block may not have: then the chain
+   const int ncomp = min(CG, nw - c0);
+   constexpr bool kMfold = MOMT == 1 && kFoldMfmaOk;
+   const bool mfold = kMfold && fold && 128 * ncomp <= Bp;
+   double tapa[2] = {0.0, 0.0};
+   if (mfold && wave < ncomp) fold_tap_operand<REC>(tapa, lane);
    __syncthreads();
    if (TIMELINE) stamp(2);
 
-   // fold moments into the 64-cell partial grid of every window of this group:
-   //   g[gi] = sum_t sum_d C[t][d] M[(gi + m - t) mod 64][d]
-   const int ncomp = min(CG, nw - c0);
-   for (int idx = tid; idx < ncomp * kNos; idx += THREADS) {
+   for (int cl = wave; kMfold && mfold && cl < ncomp; cl += nwaves) {
+      const double v = fold_window_mfma(tapa, s_mom + mom_index<1>(cl, 0, 0), s_alpha + cl * 128, lane);
+      if (gsum)
+         atomicAdd(gsum + (size_t)(c0 + cl) * kNos + lane, v);  // launch_spread_grid's atomic sum
+      else
+         part[((size_t)(c0 + cl) * nblocks + b) * kNos + lane] = v;  // [comp][block][cell]
+   }
+   for (int idx = tid; !mfold && idx < ncomp * kNos; idx += THREADS) {
       const int cl = idx / kNos;
       const int gi = idx % kNos;
       double v = 0.0;
@@ -1155,7 +1223,7 @@ int upload_tap_coeffs()
 }
 
 typedef void (*SpreadFn)(const uint16_t*, const uint32_t*, const uint32_t*, const int*, const int*, const double*, int,
-                         int, int, int, int, int, double*, double*);
+                         int, int, int, int, int, double*, double*, int);
 // 0: the spread; 1: the same with per-workgroup s_memrealtime stamps (tools/timeline_spread.py); 2: the round-4
 // moment table (MOMT 0, A/B).  Variants that measured slower or neutral (prefetching runs, persistent workgroups,
 // several groups per workgroup, the fold in two chains, register-staged alpha, the row shards' block sum in the
@@ -1310,7 +1378,7 @@ static int launch_spread_to(const AdditivePlan& P, const double* d_x, double* d_
    const int gridx = ((P.nblocks + 7) / 8) * 8 * P.ngroups;
    launch_ev(fn, dim3(gridx), dim3(kSpreadThreads), spread_lds_bytes(P), stream, P.kev ? P.kev + 0 : nullptr,
              P.dl.meta, P.dl.lo, P.dl.q, P.dl.tile_off, (const int*)P.dl.cmax, d_x, P.n, P.B, P.nblocks, P.ngroups,
-             P.CG, P.nw, d_part, d_gsum);
+             P.CG, P.nw, d_part, d_gsum, P.spread_fold);
    NFFT4GP_HIP_CHECK(hipGetLastError());
    return 0;
 }

@@ -4,13 +4,15 @@
 # one setting per word, several variables of one setting joined by commas.  AB_CONFIGS runs every setting on
 # several workloads, bench argument sets separated by ';', e.g. config E in both record precisions and config C:
 #   AB_CONFIGS="--n 10000000 --d 64 --steps 100 --precision 32;--n 10000000 --d 64 --steps 100;--steps 500"
+# the spread's fold as the chain / on the matrix unit, AB_REPS (default 2) reps:
+#   AB_REPS=3 bash tools/ab_env.sh "NFFT4GP_AMD_SPREAD_FOLD=0 NFFT4GP_AMD_SPREAD_FOLD=1" --steps 500
 set -o pipefail
 OUT="${NFFT4GP_OUT:-bench_out}"; export OUT
 mkdir -p "$OUT"
 SETS="$1"; shift
 IFS=';' read -r -a CFGS <<< "${AB_CONFIGS:-}"
 if [ ${#CFGS[@]} -eq 0 ]; then CFGS=(""); fi
-for rep in 1 2; do
+for rep in $(seq 1 "${AB_REPS:-2}"); do
   for cfg in "${CFGS[@]}"; do
     i=0
     for kv in $SETS; do

@@ -516,7 +516,13 @@ const char *Nfft4GPAmdVersion(void);
 
 /* layout statistics of an additive handle after its first setup:
  * out[0]=n, [1]=nwindows, [2]=block size, [3]=#blocks, [4]=#tiles, [5]=slots (incl. padding),
- * [6]=points per chunk R, [7]=comps per group, [8]=#groups, [9]=device bytes of the layout */
+ * [6]=points per chunk R, [7]=comps per group, [8]=#groups, [9]=device bytes of the layout;
+ * what the matvec's launchers pick for this handle now (its layout, its deterministic mode, the
+ * NFFT4GP_AMD_* variables): [10]=spread variant (0-3), [11]=1 if the spread adds its grids with global
+ * atomics (0: partial grids, summed by the grid kernel), [12]=threads per interpolation workgroup (512 or
+ * 1024), [13]=1 if a plain matvec (no gradient, no fused dot) takes the LDS-staged interpolation
+ * (k_interp_hl), [14]=that kernel's staging slots, [15]=threads per two-vector interpolation workgroup.
+ * Only the first nout entries are written. */
 int Nfft4GPAmdAdditiveLayoutInfo(void *str, long long *out, int nout);
 
 /* per-kernel timing with hipEvents on the library stream (0 disables; resets counters when enabled).

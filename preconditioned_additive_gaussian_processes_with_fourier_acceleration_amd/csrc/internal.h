@@ -299,6 +299,14 @@ int launch_interp_blocks(const AdditivePlan& P, double alpha, const double* d_x,
 // y_v = beta y_v + alpha A x_v, v = 0, 1, in one pass over the layout (1-D layouts; -1 for multi-feature windows)
 int launch_matvec2(AdditivePlan& P, double alpha, const double* x0, const double* x1, double beta, double* y0,
                    double* y1, hipStream_t stream);
+// What the launchers pick for a handle, one function per decision: the launchers call them and so does
+// Nfft4GPAmdAdditiveLayoutInfo (out[10 .. 15]), so a test can tell which kernel a matvec ran
+int pick_spread_variant(const AdditivePlan& P);   // k_spread variant 0 - 3
+bool grid_atomic(const AdditivePlan& P);          // the spread adds into d_gsum (no partial grids)
+int pick_interp_threads(const AdditivePlan& P);   // launch_interp's workgroup: 512 or 1024
+bool pick_interp_hl(const AdditivePlan& P);       // a plain matvec (no gradient, no fused dot) takes k_interp_hl
+int pick_hl_slots(const AdditivePlan& P);         // k_interp_hl's staging slots ns
+int pick_interp2_threads();                       // k_interp2's workgroup: 512 or 1024
 // y_v = beta y_v + alpha A x_v for nv device vectors of this library's additive handle (pairs per layout pass)
 int additive_matvec_multi(void* str, int nv, double alpha, const double* const* X, double beta, double* const* Y);
 // y = A x (alpha = 1, beta = 0) and *d_dot = (y, x) on device pointers: the matvec + dot of a CG step in

@@ -914,9 +914,11 @@ int Nfft4GPAmdAdditiveLayoutInfo(void* str, long long* out, int nout)
    PlanExt* E = additive_plan(str);
    if (!E || !out) return -1;
    const AdditivePlan& P = E->P;
-   long long v[10] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
-                      (long long)P.dl.bytes};
-   for (int i = 0; i < nout && i < 10; i++) out[i] = v[i];
+   // [10 .. 15]: the launchers' own decisions (internal.h pick_*), for the handle as it stands now
+   long long v[16] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
+                      (long long)P.dl.bytes, pick_spread_variant(P), grid_atomic(P), pick_interp_threads(P),
+                      pick_interp_hl(P), pick_hl_slots(P), pick_interp2_threads()};
+   for (int i = 0; i < nout && i < 16; i++) out[i] = v[i];
    return 0;
 }
 

@@ -947,6 +947,7 @@ __global__ __launch_bounds__(THREADS) void k_interp(
 // group every wave has left two groups before, and the stager stages before it waits for anything, so the waves
 // never wait on one another in a cycle.  Same arithmetic as k_interp's plain path (bitwise equal results).
 constexpr int kHlWin = kNC * kNos + 1;
+constexpr size_t kMaxDynamicLds = 160 * 1024;  // a workgroup's LDS on gfx950 (raise_lds_limit_once)
 
 __host__ __device__ constexpr size_t hl_lds_bytes(int B, int CG, int ngroups, int ns)
 {
@@ -1244,12 +1245,15 @@ constexpr int kNumSpreadVariants = 4;
 // current tile's moments (variant 3; E32 606 -> 584 us, E64 739 -> 719), which costs 1.8 % on a cache-resident
 // layout (config C, 175 MB), so the choice follows the layout's size (profiles/r06_matvec_variants_ab.txt)
 constexpr size_t kInfinityCacheBytes = 256ull << 20;
-static SpreadFn spread_fn(const AdditivePlan& P)
+int pick_spread_variant(const AdditivePlan& P)
 {
    int v = P.spread_variant;
    if (v < 0) v = P.dl.bytes > kInfinityCacheBytes ? 3 : 0;
-   v = std::min(v, kNumSpreadVariants - 1);
-   return kSpreadFns[P.rec == 4 ? 1 : 0][P.det ? 1 : 0][v];
+   return std::min(v, kNumSpreadVariants - 1);
+}
+static SpreadFn spread_fn(const AdditivePlan& P)
+{
+   return kSpreadFns[P.rec == 4 ? 1 : 0][P.det ? 1 : 0][pick_spread_variant(P)];
 }
 
 constexpr int kInterpThreads = 1024;
@@ -1312,10 +1316,35 @@ static InterpHlFn interp_hl_fn(bool small, bool det, int rec)
 // on a cache-resident layout (config C) its one-wave stagings stall the waves, which there run about one tile per
 // group (31 -> 42 us), so k_interp stays.  NFFT4GP_AMD_INTERP_HL=0 / 1 forces either
 // (profiles/r06_matvec_variants_ab.txt)
-static bool interp_hl_on(const AdditivePlan& P)
+bool pick_interp_hl(const AdditivePlan& P)
 {
    static const int v = getenv("NFFT4GP_AMD_INTERP_HL") ? atoi(getenv("NFFT4GP_AMD_INTERP_HL")) : -1;
-   return v < 0 ? P.dl.bytes > kInfinityCacheBytes : v != 0;
+   return (v < 0 ? P.dl.bytes > kInfinityCacheBytes : v != 0) && P.ngroups >= 1;
+}
+// 512-thread workgroups once there are >= 512 blocks (two workgroups per CU overlap one another's prologue
+// and epilogue: 787 -> 734 us at config E; with fewer blocks half the CU would idle, 30.8 -> 34.3 us at
+// config C; profiles/r04_interp_threads_ab.txt).  NFFT4GP_AMD_INTERP_THREADS=512 / 1024 forces either.
+int pick_interp_threads(const AdditivePlan& P)
+{
+   static const int forced = getenv("NFFT4GP_AMD_INTERP_THREADS") ? atoi(getenv("NFFT4GP_AMD_INTERP_THREADS")) : 0;
+   return forced == 512 || (forced != 1024 && P.nblocks >= 512) ? 512 : kInterpThreads;
+}
+// k_interp_hl's staging slots: 2 on 512-thread workgroups (two per CU fit 2 x 81 KB of LDS), up to 6 on 1024
+int pick_hl_slots(const AdditivePlan& P)
+{
+   static const int slots_env = getenv("NFFT4GP_AMD_HL_SLOTS") ? atoi(getenv("NFFT4GP_AMD_HL_SLOTS")) : 0;
+   int ns = std::max(2, std::min(slots_env > 0 ? slots_env : 2, pick_interp_threads(P) == 512 ? 2 : 6));
+   // no more than a workgroup's 160 KB of LDS holds beside the y slice (a forced 6 with NFFT4GP_AMD_CG=8 and
+   // blocks of 4064 points would ask for 229 KB, more than a launch can have: 3 fit)
+   while (ns > 2 && hl_lds_bytes(P.B, P.CG, P.ngroups, ns) > kMaxDynamicLds) ns--;
+   return ns;
+}
+// k_interp2 on 1024 threads: 512-thread workgroups at config E's 2461 blocks measured the same loss (1.700 s either
+// way, profiles/r05_interp2_ab.txt); NFFT4GP_AMD_INTERP2_THREADS=512 selects them
+int pick_interp2_threads()
+{
+   static const int forced = getenv("NFFT4GP_AMD_INTERP2_THREADS") ? atoi(getenv("NFFT4GP_AMD_INTERP2_THREADS")) : 0;
+   return forced == 512 ? 512 : kInterp2Threads;
 }
 
 static std::vector<const void*> interp_kernels()
@@ -1343,9 +1372,9 @@ static void raise_lds_limit_once()
       for (const auto& byrec : kSpreadFns)
          for (const auto& bydet : byrec)
             for (const SpreadFn f : bydet)
-               (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+               (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
       for (const void* f : interp_kernels())
-         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
       (void)hipGetLastError();
       return true;
    }();
@@ -1394,7 +1423,7 @@ int launch_spread(const AdditivePlan& P, const double* d_x, double* d_part, hipS
 // window, most of k_grid's 5 us.  The sums' order then follows the workgroups' arrival, so deterministic mode keeps
 // the partials; with many blocks (config E: 2461 adds per address) the adds would contend, so they keep them too.
 constexpr int kAtomicGridMaxBlocks = 512;
-static bool grid_atomic(const AdditivePlan& P)
+bool grid_atomic(const AdditivePlan& P)
 {
    static const int v = getenv("NFFT4GP_AMD_GRID_ATOMIC") ? atoi(getenv("NFFT4GP_AMD_GRID_ATOMIC")) : -1;
    if (P.det || v == 0) return false;
@@ -1500,15 +1529,9 @@ int launch_interp(const AdditivePlan& P, int grad, double alpha, const double* d
       fprintf(stderr, "nfft4gp_amd: fused matvec-dot needs a plain matvec and <= %d blocks\n", kRedMaxBlocks);
       return -1;
    }
-   // 512-thread workgroups once there are >= 512 blocks (two workgroups per CU overlap one another's prologue
-   // and epilogue: 787 -> 734 us at config E; with fewer blocks half the CU would idle, 30.8 -> 34.3 us at
-   // config C; profiles/r04_interp_threads_ab.txt).  NFFT4GP_AMD_INTERP_THREADS=512 / 1024 forces either.
-   static const int forced = getenv("NFFT4GP_AMD_INTERP_THREADS") ? atoi(getenv("NFFT4GP_AMD_INTERP_THREADS")) : 0;
-   const bool small = forced == 512 || (forced != 1024 && P.nblocks >= 512);
-   if (!grad && !d_dot && interp_hl_on(P) && P.ngroups >= 1) {
-      // staging slots: 2 on 512-thread workgroups (two per CU fit 2 x 81 KB of LDS), up to 6 on 1024
-      static const int slots_env = getenv("NFFT4GP_AMD_HL_SLOTS") ? atoi(getenv("NFFT4GP_AMD_HL_SLOTS")) : 0;
-      const int ns = std::max(2, std::min(slots_env > 0 ? slots_env : 2, small ? 2 : 6));
+   const bool small = pick_interp_threads(P) == 512;
+   if (!grad && !d_dot && pick_interp_hl(P)) {
+      const int ns = pick_hl_slots(P);
       launch_ev(interp_hl_fn(small, P.det, P.rec), dim3(P.nblocks), dim3(small ? 512 : kInterpThreads),
                 hl_lds_bytes(P.B, P.CG, P.ngroups, ns), stream, P.kev ? P.kev + 4 : nullptr, P.dl.meta, P.dl.lo,
                 P.dl.q, P.dl.tile_off, (const double*)P.d_H, d_x, d_y, P.n, P.B, P.ngroups, P.CG, P.nw, alpha, beta,
@@ -1565,10 +1588,7 @@ int launch_matvec2(AdditivePlan& P, double alpha, const double* x0, const double
                       (const double*)P.d_w, (const double*)P.d_wd, P.d_H2, P.d_Hd, 0, 0, (long long)part_rs,
                       (long long)h_rs, P.det ? P.d_hb : (double*)nullptr, 0);
    const size_t lds_i = sizeof(double) * 2 * ((size_t)P.B + kPad);
-   // 1024 threads: 512-thread workgroups at config E's 2461 blocks measured the same loss (1.700 s either way,
-   // profiles/r05_interp2_ab.txt); NFFT4GP_AMD_INTERP2_THREADS=512 selects them
-   static const int forced = getenv("NFFT4GP_AMD_INTERP2_THREADS") ? atoi(getenv("NFFT4GP_AMD_INTERP2_THREADS")) : 0;
-   const bool small = forced == 512;
+   const bool small = pick_interp2_threads() == 512;
    hipLaunchKernelGGL(interp2_fn(P.det, small, P.rec), dim3(P.nblocks), dim3(small ? 512 : kInterp2Threads), lds_i, stream,
                       P.dl.meta, P.dl.lo,
                       P.dl.q, P.dl.tile_off, (const double*)P.d_H2, h_rs, x0, x1, y0, y1, P.n, P.B, P.ngroups, alpha,

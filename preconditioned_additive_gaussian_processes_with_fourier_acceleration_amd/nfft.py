@@ -191,10 +191,13 @@ class NFFTAdditiveKernel:
 
     # ---- introspection ---------------------------------------------------------------------------
     def layout_info(self) -> dict:
-        out = (C.c_longlong * 10)()
-        _lib.lib().Nfft4GPAmdAdditiveLayoutInfo(self.h, out, 10)
+        """The layout's statistics, and what the matvec's launchers pick for this handle as it stands
+        (spread_variant .. interp2_threads: include/nfft4gp_amd.h, Nfft4GPAmdAdditiveLayoutInfo)."""
+        out = (C.c_longlong * 16)()
+        _lib.lib().Nfft4GPAmdAdditiveLayoutInfo(self.h, out, 16)
         keys = ["n", "nwindows", "block", "nblocks", "ntiles", "slots", "R", "comps_per_group", "ngroups",
-                "layout_bytes"]
+                "layout_bytes", "spread_variant", "grid_atomic", "interp_threads", "interp_hl", "hl_slots",
+                "interp2_threads"]
         return dict(zip(keys, [int(v) for v in out]))
 
     def set_deterministic(self, on: bool = True):

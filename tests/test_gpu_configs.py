@@ -373,6 +373,8 @@ def test_config_e_full_size_properties(torch_cuda):
     op = amd.NFFTAdditiveKernel(X, win, d, 1)
     l = 0.1
     assert op.setup(amd.GAUSSIAN, 1.0, l, 0.01) == 0
+    info = op.layout_info()
+    assert info["interp_hl"] == 1 and info["spread_variant"] == 3, info  # the rule for layouts past 256 MB
     rng = np.random.default_rng(8)
     u = torch.tensor(rng.random(n) - 0.5, device="cuda")
     v = torch.tensor(rng.random(n) - 0.5, device="cuda")

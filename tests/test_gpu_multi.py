@@ -59,6 +59,8 @@ def test_multi_past_the_infinity_cache_is_bitwise(torch_cuda):
     del X
     assert op.setup(amd.GAUSSIAN, f=1.0, l=0.5, mu=0.01) == 0
     op.set_deterministic(True)
+    info = op.layout_info()
+    assert info["interp_hl"] == 1 and info["spread_variant"] == 3, info  # the rule for layouts past 256 MB
     V = torch.tensor(rng.random((2, n)) - 0.5, device="cuda")
     Y1 = torch.empty_like(V)
     Y2 = torch.empty_like(V)

@@ -867,6 +867,40 @@ int Nfft4GPAmdModelCoefficients(void *model, NFFT4GP_DOUBLE *H, NFFT4GP_DOUBLE *
 void *Nfft4GPAmdModelFromCoefficients(int nw, int d, int kernel, const NFFT4GP_DOUBLE *hyper3,
                                       const NFFT4GP_DOUBLE *H, const NFFT4GP_DOUBLE *centre,
                                       const NFFT4GP_DOUBLE *scale, const int *feature);
+/* ---- the predictive standard deviation of a fitted model --------------------------------
+ * With 1-D windows the operator is a finite-rank kernel, A = f^2 (Z W Z^T + mu I).  Per window c, with
+ * xs = (x - centre_c) scale_c quantised as Nfft4GPAmdModelPredict does, the features are
+ *   phi_c(xs) = [cos 2 pi k xs, k = 0..16 | sin 2 pi k xs, k = 1..16]          (33 per window)
+ * and the model's features are the windows' blocks in window order, R = 33 nw.  W is diagonal
+ * (Nfft4GPAmdModelFeatureWeights) and may have negative entries.  With G = Z^T Z over the training points and
+ *   S = mu (mu I + W G)^{-1} W        (symmetric, R x R; solved by LU: no Cholesky, no W^1/2, no W^-1)
+ * the predictive standard deviation is std(x*) = sqrt| f^2 (mu + phi*^T S phi*) |: the reference's
+ * K22ii - k*^T A^{-1} k* with its noise term and its fabs (nfft_interface.c:1054), without a solve, without
+ * the training data at serving time, and independent of which points are predicted together.
+ * Nfft4GPAmdModelFitVariance: builds S from the training points X (n x d column-major, leading dimension ldim,
+ * host or device) and the model's own centres, scales, features, kernel and (f, l, mu); it does not use the
+ * operator, so a model loaded from coefficients can be fitted.  Deterministic: two calls give the same bits.
+ * 0; -1 bad arguments, more than 128 windows (S would exceed 170 MB), or a failed LU (mu = 0); -2 when a row
+ * of X lies outside the model's domain (count on stderr; the model, a previous S included, is unchanged). */
+int Nfft4GPAmdModelFitVariance(void *model, const NFFT4GP_DOUBLE *X, int n, int ldim, int d);
+/* std[i] for the n_new rows of Xnew, with the conventions of Nfft4GPAmdModelPredict (host or device
+ * pointers, NaN and *n_outside for points outside the domain, n_new = 0 accepted).  with_noise = 0 drops
+ * the mu term.  A point's bits depend on neither its place in the batch nor the batch size.  -3 when the
+ * model holds no variance. */
+int Nfft4GPAmdModelPredictStd(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d,
+                              NFFT4GP_DOUBLE *std, int with_noise, long long *n_outside);
+/* wall clock of the model's last successful fit in ms: features, Grams and their sum, system + LU + symmetrise */
+int Nfft4GPAmdModelFitTimes(void *model, NFFT4GP_DOUBLE *ms3);
+/* *R = 33 nw when the model holds a variance, else 0 */
+int Nfft4GPAmdModelVarianceInfo(void *model, int *R);
+/* S to / from the host: R x R, row-major, unpadded, in the feature order above (-3: none held; R must be
+ * 33 nw) */
+int Nfft4GPAmdModelVariance(void *model, NFFT4GP_DOUBLE *S);
+int Nfft4GPAmdModelSetVariance(void *model, const NFFT4GP_DOUBLE *S, int R);
+/* host only, no device needed: the 33 weights of one window of scale `scale` among nw, from b^ =
+ * the kernel's Fourier coefficients at the window's sigma (index k + 16, k = -16..15):
+ * w[cos 0] = b^_0 / nw; w[cos k] = w[sin k] = 2 b^_k / nw, k = 1..15; w[cos 16] = w[sin 16] = b^_-16 / nw */
+int Nfft4GPAmdModelFeatureWeights(int kernel, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE scale, int nw, NFFT4GP_DOUBLE *w33);
 void Nfft4GPAmdModelFree(void *model);
 
 /* ---- host-only helpers (no GPU needed): the setup math of the device plan, exported so the CPU
@@ -901,6 +935,9 @@ int Nfft4GPAmdDeviceLayoutRec(const unsigned int *qc, int n, int nw, int B, int 
  * (returns 0, or the failing column + 1 if A + shift I is not positive definite) */
 int Nfft4GPAmdHostSymEig(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *w, NFFT4GP_DOUBLE *V);
 int Nfft4GPAmdHostCholInverse(const NFFT4GP_DOUBLE *A, int k, NFFT4GP_DOUBLE shift, NFFT4GP_DOUBLE *G);
+/* the host fallback of the model variance's LU (used when rocSOLVER cannot be loaded): B <- A^{-1} B by LU with
+ * partial pivoting, A n x n general, B n x nrhs, column-major; 0, the first zero pivot's column + 1, or -1 */
+int Nfft4GPAmdHostLuSolve(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *B, int nrhs);
 
 #ifdef __cplusplus
 }

@@ -269,12 +269,21 @@ _SIGS = {
     "Nfft4GPAmdModelInfo": (C.c_int, [vp, ip, ip, ip, dp]),
     "Nfft4GPAmdModelCoefficients": (C.c_int, [vp, vp, vp, vp, vp]),
     "Nfft4GPAmdModelFromCoefficients": (vp, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "Nfft4GPAmdModelFitVariance": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]),
+    "Nfft4GPAmdModelPredictStd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                            C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdModelVarianceInfo": (C.c_int, [vp, ip]),
+    "Nfft4GPAmdModelFitTimes": (C.c_int, [vp, dp]),
+    "Nfft4GPAmdModelVariance": (C.c_int, [vp, vp]),
+    "Nfft4GPAmdModelSetVariance": (C.c_int, [vp, vp, C.c_int]),
+    "Nfft4GPAmdModelFeatureWeights": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
     "Nfft4GPAmdModelFree": (None, [vp]),
     "Nfft4GPAmdHostTapPoly": (C.c_int, [vp]),
     "Nfft4GPAmdHostCirculant": (C.c_int, [C.c_int, C.c_double, C.c_double, vp, vp]),
     "Nfft4GPAmdHostPrepare": (C.c_double, [vp, C.c_int, vp]),
     "Nfft4GPAmdHostSymEig": (C.c_int, [vp, C.c_int, vp, vp]),
     "Nfft4GPAmdHostCholInverse": (C.c_int, [vp, C.c_int, C.c_double, vp]),
+    "Nfft4GPAmdHostLuSolve": (C.c_int, [vp, C.c_int, vp, C.c_int]),
     "Nfft4GPAmdHostLayout": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), vp, vp,
                                        vp, vp]),
     "Nfft4GPAmdDeviceLayout": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), vp, vp,

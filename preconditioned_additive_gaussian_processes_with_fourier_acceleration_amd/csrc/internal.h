@@ -348,6 +348,10 @@ int gemm_f64(bool transA, int M, int N, int K, const double* A, long long lda, c
              double* C, long long ldc, hipStream_t s);
 int sym_eig_host(const std::vector<double>& A, int n, std::vector<double>& w, std::vector<double>& V);
 int chol_inverse_host(std::vector<double>& A, int k);
+// B <- A^{-1} B, A n x n general, B n x nrhs, column-major: LU with partial pivoting on the host, and on device
+// arrays (ld n) by rocSOLVER getrf / getrs with the host LU as the fallback; 0, zero pivot column + 1, or -1
+int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs);
+int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s);
 struct Comm;
 // a row shard of the Nystrom setup: this process holds rows [row_begin, row_begin + n) of n_global; the
 // Gram is all-reduced over comm and rank 0's k x k factors are broadcast (dist.hip)

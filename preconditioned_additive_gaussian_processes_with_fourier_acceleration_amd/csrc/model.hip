@@ -17,6 +17,10 @@
 // regularised periodic kernel is the kernel; a new point within that radius has the same guarantee, one outside
 // it does not (NaN, counted).  The half fixed-point unit of slack keeps inside the training point that defines
 // the radius, whose (x - c) * (0.25 / r) may round one ulp above 1/4.
+//
+// The second half of the file is the predictive standard deviation: the operator's finite-rank form gives the
+// posterior variance as a quadratic form in a point's trigonometric features (see "the predictive variance").
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,11 +48,15 @@ struct Model {
    int* d_feature = nullptr;    // [nw]
    unsigned int* d_cnt = nullptr;  // per-workgroup counts of outside points (grown on demand)
    size_t cnt_cap = 0;
+   double* d_S = nullptr;  // the variance matrix, mv_order(nw)^2, symmetric, windows kMvPad slots apart; or none
+   int R = 0;              // 33 nw once a variance is held, else 0
+   double fit_ms[3] = {0.0, 0.0, 0.0};  // the last fit's wall clock: features, Grams and their sum, system + LU
 };
 
 void model_free(Model* M)
 {
    if (!M) return;
+   if (M->d_S) (void)hipFree(M->d_S);
    if (M->d_H) (void)hipFree(M->d_H);
    if (M->d_centre) (void)hipFree(M->d_centre);
    if (M->d_scale) (void)hipFree(M->d_scale);
@@ -227,6 +235,464 @@ int model_predict(Model* M, const double* Xnew, int n_new, long long ldim, doubl
    return rc;
 }
 
+// ---- the predictive variance ---------------------------------------------------------------------------------
+// With 1-D windows the operator is a finite-rank kernel, A = f^2 (Z W Z^T + mu I): Z holds per window the 33
+// features [cos 2 pi k xs, k = 0..16 | sin 2 pi k xs, k = 1..16] of the window's scaled coordinate and W is
+// diagonal (feature_weights).  The posterior variance at a point with features phi is f^2 (mu + phi^T S phi) with
+// S = mu (mu I + W G)^{-1} W, G = Z^T Z over the training points: no solve and no training data at serving time.
+// W has negative entries (the regularised periodic kernel's b^ are not all positive), so mu I + W G is solved as
+// the nonsymmetric matrix it is, by LU; S itself is symmetric (W - W G (mu I + W G)^{-1} W) and is stored as
+// (S + S^T) / 2.  Internally a window takes kMvPad = 36 slots (33 features and 3 zeros: a whole number of MFMA k
+// steps) and the windows are padded to a multiple of 4 (k_model_std's column tile), R_p = 36 * 4 ceil(nw / 4); the
+// added slots have zero features and zero weight, so mu I + W G keeps mu on their diagonal and S is zero there.
+typedef double d4 __attribute__((ext_vector_type(4)));
+constexpr int kMvFeat = 33, kMvPad = 36, kMvMaxNw = 128;  // S at 128 windows: 4608^2 doubles = 170 MB
+inline int mv_order(int nw) { return kMvPad * ((nw + 3) / 4 * 4); }  // R_p
+
+// cos and sin of 2 pi xs_q, xs_q the window's quantised coordinate (quantize(): what k_model_predict decodes its
+// cell and offset from); false when the point is outside the window's domain (the angle is then 0)
+__device__ inline bool mv_angle(double x, double ctr, double sc, double& c1, double& s1)
+{
+   const double xs = (x - ctr) * sc;
+   const bool in = fabs(xs) <= kMpLimit;
+   const double xq = in ? xs : 0.0;
+   const uint32_t q = (uint32_t)(unsigned long long)llround(xq * 4294967296.0);
+   sincospi((double)(int)q * (1.0 / 2147483648.0), &s1, &c1);  // |xs| <= 1/4: (int)q 2^-32 is xs_q
+   return in;
+}
+
+// (cos, sin) k theta -> (k + 1) theta: a rotation, whose error grows linearly in k (<= 16 steps)
+__device__ inline void mv_rotate(double& ck, double& sk, double c1, double s1)
+{
+   const double c = ck * c1 - sk * s1;
+   sk = sk * c1 + ck * s1;
+   ck = c;
+}
+
+// per workgroup the number of rows with a coordinate outside some window's domain
+__global__ __launch_bounds__(256) void k_model_outside(const double* __restrict__ centre,
+                                                       const double* __restrict__ scale,
+                                                       const int* __restrict__ feature, int nw,
+                                                       const double* __restrict__ X, long long ldim, int n,
+                                                       unsigned int* __restrict__ cnt_out)
+{
+   __shared__ unsigned int s_cnt[256 / kWave];
+   const int tid = threadIdx.x;
+   const long long i = (long long)blockIdx.x * 256 + tid;
+   bool out = false;
+   if (i < n)
+      for (int c = 0; c < nw; c++) {
+         const double xs = (X[(size_t)feature[c] * (size_t)ldim + i] - centre[c]) * scale[c];
+         out = out || !(fabs(xs) <= kMpLimit);
+      }
+   const unsigned int cnt = (unsigned int)__popcll(__ballot(out));
+   if ((tid & (kWave - 1)) == 0) s_cnt[tid / kWave] = cnt;
+   __syncthreads();
+   if (tid == 0) {
+      unsigned int t = 0;
+      for (int w = 0; w < 256 / kWave; w++) t += s_cnt[w];
+      cnt_out[blockIdx.x] = t;
+   }
+}
+
+// Z[(36 c + j) ldz + i] = feature j of window c at point i0 + i, i < cnt: a chunk of Z, column-major [feature][point];
+// blockIdx.y runs over the padded windows, those >= nw are zero
+__global__ __launch_bounds__(256) void k_model_features(const double* __restrict__ centre,
+                                                        const double* __restrict__ scale,
+                                                        const int* __restrict__ feature, int nw,
+                                                        const double* __restrict__ X, long long ldim, long long i0,
+                                                        int cnt, double* __restrict__ Z, long long ldz)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+   if (i >= cnt) return;
+   double* z = Z + (size_t)c * kMvPad * ldz + i;
+   if (c >= nw) {
+      for (int j = 0; j < kMvPad; j++) z[j * ldz] = 0.0;
+      return;
+   }
+   double c1, s1;
+   (void)mv_angle(X[(size_t)feature[c] * (size_t)ldim + i0 + i], centre[c], scale[c], c1, s1);
+   double ck = 1.0, sk = 0.0;
+#pragma unroll
+   for (int k = 0; k <= 16; k++) {
+      z[k * ldz] = ck;
+      if (k) z[(16 + k) * ldz] = sk;
+      mv_rotate(ck, sk, c1, s1);
+   }
+   for (int j = kMvFeat; j < kMvPad; j++) z[j * ldz] = 0.0;
+}
+
+__global__ void k_model_add(double* __restrict__ G, const double* __restrict__ Gc, long long count)
+{
+   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+   if (i < count) G[i] += Gc[i];
+}
+
+// A = mu I + W G and B = mu W (both R_p x R_p column-major): S = A^{-1} B
+__global__ void k_model_system(const double* __restrict__ G, const double* __restrict__ w, int Rp, double mu,
+                               double* __restrict__ A, double* __restrict__ B)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i >= Rp) return;
+   const size_t e = i + (size_t)j * Rp;
+   A[e] = w[i] * G[e] + (i == j ? mu : 0.0);
+   B[e] = (i == j) ? mu * w[i] : 0.0;
+}
+
+__global__ void k_model_symmetrise(const double* __restrict__ B, int Rp, double* __restrict__ S)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i < Rp) S[i + (size_t)j * Rp] = 0.5 * (B[i + (size_t)j * Rp] + B[j + (size_t)i * Rp]);
+}
+
+// the 33 weights of one window: w[cos 0] = b^_0 / nw, w[cos k] = w[sin k] = 2 b^_k / nw (k = 1..15),
+// w[cos 16] = w[sin 16] = b^_{-16} / nw (the band's one unpaired mode), b^ indexed k + 16
+void feature_weights(int kernel, double l, double scale, int nw, double* w33)
+{
+   double bh[kBand];
+   const double sig = (kernel == 0) ? l * scale * std::sqrt(2.0) : l * scale;  // plan_setup's comp_sigma
+   bhat_1d(kernel == 0 ? 0 : 2, sig, bh);
+   w33[0] = bh[16] / nw;
+   for (int k = 1; k <= 15; k++) w33[k] = w33[16 + k] = 2.0 * bh[16 + k] / nw;
+   w33[16] = w33[32] = bh[0] / nw;
+}
+
+// X (n x d, ld ldim; host or device) as a device array: *dX, *ld; *owned is to be freed by the caller
+int stage_points(const Model* M, const double* X, int n, long long ldim, hipStream_t s, const double** dX,
+                 long long* ld, double** owned)
+{
+   *owned = nullptr;
+   *dX = X;
+   *ld = ldim;
+   if (is_device_ptr(X)) return 0;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)owned, sizeof(double) * (size_t)n * M->d));
+   NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(*owned, sizeof(double) * (size_t)n, X, sizeof(double) * (size_t)ldim,
+                                      sizeof(double) * (size_t)n, (size_t)M->d, hipMemcpyHostToDevice, s));
+   *dX = *owned;
+   *ld = n;
+   return 0;
+}
+
+int grow_counts(Model* M, size_t nblk)
+{
+   if (nblk <= M->cnt_cap) return 0;
+   if (M->d_cnt) (void)hipFree(M->d_cnt);
+   M->d_cnt = nullptr;
+   M->cnt_cap = 0;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)&M->d_cnt, sizeof(unsigned int) * nblk));
+   M->cnt_cap = nblk;
+   return 0;
+}
+
+int read_counts(Model* M, size_t nblk, hipStream_t s, long long* total)
+{
+   std::vector<unsigned int> h(nblk);
+   NFFT4GP_HIP_CHECK(hipMemcpyAsync(h.data(), M->d_cnt, sizeof(unsigned int) * nblk, hipMemcpyDeviceToHost, s));
+   NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+   long long t = 0;
+   for (unsigned int v : h) t += v;
+   *total = t;
+   return 0;
+}
+
+// points per chunk of Z: the chunk stays <= 256 MB
+int chunk_points(int n, int Rp)
+{
+   const long long cap = std::max<long long>(1024, (32LL << 20) / Rp / 16 * 16);
+   return (int)std::min<long long>(n, cap);
+}
+
+// The fit: Z in chunks -> their Grams (gram_tn: split sum in a fixed order) added in chunk order -> mu I + W G
+// -> LU -> S.  Every step is deterministic, so two fits give the same bits.  Returns 0, -1, or -2 (rows outside).
+int model_fit_variance(Model* M, const double* X, int n, long long ldim)
+{
+   hipStream_t s = current_stream();
+   const int nw = M->nw, Rp = mv_order(nw);
+   const size_t rr = (size_t)Rp * Rp;
+   double *xown = nullptr, *Z = nullptr, *G = nullptr, *Gc = nullptr, *A = nullptr, *S = nullptr, *d_w = nullptr;
+   auto body = [&]() -> int {
+      const double* dX;
+      long long ld;
+      if (stage_points(M, X, n, ldim, s, &dX, &ld, &xown)) return -1;
+      const size_t nblk = ((size_t)n + 255) / 256;
+      long long outside = 0;
+      if (grow_counts(M, nblk)) return -1;
+      hipLaunchKernelGGL(k_model_outside, dim3((unsigned int)nblk), dim3(256), 0, s, (const double*)M->d_centre,
+                         (const double*)M->d_scale, (const int*)M->d_feature, nw, dX, ld, n, M->d_cnt);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (read_counts(M, nblk, s, &outside)) return -1;
+      if (outside) {
+         fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdModelFitVariance: %lld of %d rows lie outside the model's domain; "
+                         "the model is unchanged.\n", outside, n);
+         return -2;
+      }
+      const int chunk = chunk_points(n, Rp);
+      const long long ldz = ((long long)chunk + 15) / 16 * 16;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Z, sizeof(double) * (size_t)ldz * Rp));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&G, sizeof(double) * rr));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Gc, sizeof(double) * rr));
+      NFFT4GP_HIP_CHECK(hipMemsetAsync(G, 0, sizeof(double) * rr, s));
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      double ms[3] = {0.0, 0.0, 0.0};
+      auto t0 = std::chrono::steady_clock::now();
+      auto lap = [&](int which) {  // the stream is idle: gram_tn and lu_solve_dev synchronise
+         const auto t1 = std::chrono::steady_clock::now();
+         ms[which] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+         t0 = t1;
+      };
+      for (long long i0 = 0; i0 < n; i0 += chunk) {
+         const int cnt = (int)std::min<long long>(chunk, n - i0);
+         hipLaunchKernelGGL(k_model_features, dim3((cnt + 255) / 256, Rp / kMvPad), dim3(256), 0, s,
+                            (const double*)M->d_centre, (const double*)M->d_scale, (const int*)M->d_feature, nw, dX,
+                            ld, i0, cnt, Z, ldz);
+         NFFT4GP_HIP_CHECK(hipGetLastError());
+         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+         lap(0);
+         if (gram_tn(Rp, Rp, cnt, Z, ldz, Z, ldz, Gc, 1, s)) return -1;
+         lap(1);
+         hipLaunchKernelGGL(k_model_add, dim3((unsigned int)((rr + 255) / 256)), dim3(256), 0, s, G,
+                            (const double*)Gc, (long long)rr);
+         NFFT4GP_HIP_CHECK(hipGetLastError());
+      }
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      lap(1);
+      (void)hipFree(Z);
+      Z = nullptr;
+      std::vector<double> w((size_t)Rp, 0.0);
+      for (int c = 0; c < nw; c++) feature_weights(M->kernel, M->l, M->scale[c], nw, w.data() + (size_t)c * kMvPad);
+      if (to_device(&d_w, w.data(), w.size())) return -1;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&A, sizeof(double) * rr));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&S, sizeof(double) * rr));
+      const dim3 g2((Rp + 255) / 256, Rp);
+      hipLaunchKernelGGL(k_model_system, g2, dim3(256), 0, s, (const double*)G, (const double*)d_w, Rp, M->mu, A, Gc);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (const int info = lu_solve_dev(A, Rp, Gc, Rp, s)) {
+         fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdModelFitVariance: the LU of mu I + W G failed (%d)%s.\n", info,
+                 M->mu == 0.0 ? "; mu is 0" : "");
+         return -1;
+      }
+      hipLaunchKernelGGL(k_model_symmetrise, g2, dim3(256), 0, s, (const double*)Gc, Rp, S);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      lap(2);
+      for (int i = 0; i < 3; i++) M->fit_ms[i] = ms[i];
+      std::swap(M->d_S, S);  // the previous matrix, if any, is freed below
+      M->R = kMvFeat * nw;
+      return 0;
+   };
+   const int rc = body();
+   (void)hipStreamSynchronize(s);
+   for (double* p : {xown, Z, G, Gc, A, S, d_w})
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
+// ---- serving: std = sqrt| f^2 (mu + phi^T S phi) | ---------------------------------------------------------------
+// k_model_std: one workgroup owns 128 points and walks S in column tiles of 144 (4 windows); per tile the product
+// Phi S[:, tile] (128 x 144) is accumulated on v_mfma_f64_16x16x4_f64 over k steps of 36 (one window).  The Phi
+// operand is generated into LDS per step: one sincospi per (point, window) and 16 rotations, four threads per
+// point each storing a quarter of the window's features.  8 waves of 16 points x 144 columns (9 MFMA blocks,
+// operands swapped as in k_gemm_f64: a lane holds the columns lane / 16 + 4 reg of 16 consecutive points).  LDS is
+// double-buffered as in k_gemm_f64: step c's MFMAs read buffer c & 1 while step c + 1's rows of S (global loads
+// issued before them) are in flight and its features are generated into the other buffer; one barrier per step.
+// The epilogue regenerates the tile's own 4 windows of features and dots them with the accumulators: Phi and
+// Phi S never reach memory.  S is symmetric, so a tile walks only the windows up to its own and doubles the
+// earlier ones' sum: 144 of 256 k steps at 32 windows.  A point's sum runs over (tile, window, block, register)
+// in a fixed order, then over its 4 lanes in lane order: its bits depend on neither its place in the batch nor
+// the batch size.
+// Measured at n_new = 1e6, 32 windows (tools/model_std_probe.py; profiles/model_std_ab.txt): 28.9 ms, 49 % of the
+// fp64 matrix peak counted at n_new R^2 flops; without the symmetry 50.2 ms; the composed route (a feature kernel,
+// gemm_f64 and a row dot, in chunks) 72.3 ms with the same values to 2e-15.  Both were removed.
+constexpr int kMsPts = 128, kMsCols = 4 * kMvPad, kMsThreads = 512;
+constexpr int kMsLdA = kMsPts + 1, kMsLdB = kMsCols + 1;
+constexpr int kMsBuf = kMvPad * (kMsLdA + kMsLdB);          // doubles per buffer: features, then rows of S
+constexpr size_t kMsLds = sizeof(double) * 2 * kMsBuf;      // 157.8 KB: one workgroup per CU
+constexpr int kMsRowGroups = 6;                             // S fetch: 72 column pairs x 6 row groups of 6 rows
+
+__global__ __launch_bounds__(kMsThreads) void k_model_std(const double* __restrict__ S, int Rp,
+                                                          const double* __restrict__ centre,
+                                                          const double* __restrict__ scale,
+                                                          const int* __restrict__ feature, int nw,
+                                                          const double* __restrict__ X, long long ldim, int n_new,
+                                                          double ff, double noise, double* __restrict__ out,
+                                                          unsigned int* __restrict__ cnt_out)
+{
+   extern __shared__ double m_smem[];
+   __shared__ unsigned int s_cnt[kMsThreads / kWave];
+   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int wm = wave * 16, lr = lane & 15, lg = lane >> 4;
+   const int p = tid & (kMsPts - 1), part = tid >> 7;  // part: 0 cos 0..8, 1 cos 9..16, 2 sin 1..8, 3 sin 9..16
+   const long long ip = (long long)blockIdx.x * kMsPts + p;
+   const bool live = ip < n_new;
+   const int fcol = 2 * (tid % (kMsCols / 2)), frow = tid / (kMsCols / 2);  // frow >= 6: no part in the S fetch
+   for (int b = 0; b < 2; b++)
+      for (int e = tid; e < (kMvPad - kMvFeat) * kMsLdA; e += kMsThreads) m_smem[b * kMsBuf + kMvFeat * kMsLdA + e] = 0.0;
+   auto xload = [&](int c) { return live ? X[(size_t)feature[c] * (size_t)ldim + ip] : centre[c]; };
+   auto gen = [&](int c, double x, double* As) {  // window c's 33 features of the 128 points into As[feature][point]
+      double c1, s1;
+      (void)mv_angle(x, centre[c], scale[c], c1, s1);
+      double ck = 1.0, sk = 0.0;
+#pragma unroll
+      for (int k = 0; k <= 16; k++) {
+         if (part == (k <= 8 ? 0 : 1)) As[k * kMsLdA + p] = ck;
+         if (k && part == (k <= 8 ? 2 : 3)) As[(16 + k) * kMsLdA + p] = sk;
+         mv_rotate(ck, sk, c1, s1);
+      }
+   };
+   double2 bv[kMvPad / kMsRowGroups];
+   double psum = 0.0;
+   const int ntile = Rp / kMsCols;
+   for (int t = 0; t < ntile; t++) {
+      auto fetch = [&](int c) {  // rows 36 c .. 36 c + 35 of S, the tile's 144 columns (R_p is a whole number of tiles)
+         const double* Sc = S + (size_t)(c * kMvPad + frow) * Rp + t * kMsCols + fcol;
+         if (frow < kMsRowGroups) {
+#pragma unroll
+            for (int u = 0; u < kMvPad / kMsRowGroups; u++)
+               bv[u] = *reinterpret_cast<const double2*>(Sc + (size_t)u * kMsRowGroups * Rp);
+         }
+      };
+      auto store = [&](double* Bs) {
+         if (frow < kMsRowGroups) {
+#pragma unroll
+            for (int u = 0; u < kMvPad / kMsRowGroups; u++) {
+               Bs[(frow + u * kMsRowGroups) * kMsLdB + fcol] = bv[u].x;
+               Bs[(frow + u * kMsRowGroups) * kMsLdB + fcol + 1] = bv[u].y;
+            }
+         }
+      };
+      d4 acc[9];
+#pragma unroll
+      for (int j = 0; j < 9; j++) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+      __syncthreads();  // the previous tile's epilogue has left both buffers
+      fetch(0);
+      gen(0, xload(0), m_smem);
+      store(m_smem + kMvPad * kMsLdA);
+      __syncthreads();
+      int cur = 0;
+      const int cend = min(nw, 4 * t + 4);  // S is symmetric: the windows after the tile's own are not walked
+      for (int c = 0; c < cend; c++) {
+         const bool more = c + 1 < cend;
+         if (c == 4 * t) {  // the windows before the tile's own count twice (exact), its own once
+#pragma unroll
+            for (int j = 0; j < 9; j++) acc[j] *= 2.0;
+         }
+         double xn = 0.0;
+         if (more) {
+            fetch(c + 1);  // in flight during this step's MFMAs
+            xn = xload(c + 1);
+         }
+         const double* As = m_smem + cur * kMsBuf;
+         const double* Bs = As + kMvPad * kMsLdA;
+#pragma unroll 3
+         for (int k4 = 0; k4 < kMvPad / 4; k4++) {
+            const int kk = 4 * k4 + lg;
+            const double a = As[kk * kMsLdA + wm + lr];
+            double b[9];
+#pragma unroll
+            for (int j = 0; j < 9; j++) b[j] = Bs[kk * kMsLdB + 16 * j + lr];
+#pragma unroll
+            for (int j = 0; j < 9; j++) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a, acc[j], 0, 0, 0);
+         }
+         if (more) {  // the other buffer: nobody reads it during this step
+            gen(c + 1, xn, m_smem + (cur ^ 1) * kMsBuf);
+            store(m_smem + (cur ^ 1) * kMsBuf + kMvPad * kMsLdA);
+         }
+         __syncthreads();
+         cur ^= 1;
+      }
+      // acc[j][rg] = (Phi S)[point wm + lr][column 144 t + 16 j + lg + 4 rg]; window wl of the tile holds the
+      // columns [36 wl, 36 wl + 36): blocks j = 36 wl / 16 .. (36 wl + 35) / 16
+#pragma unroll
+      for (int wl = 0; wl < 4; wl++) {
+         const int c = 4 * t + wl;
+         if (c < nw) {  // uniform over the workgroup
+            double* As = m_smem + (wl & 1) * kMsBuf;  // its readers of two windows ago are behind the last barrier
+            gen(c, xload(c), As);
+            __syncthreads();
+#pragma unroll
+            for (int j = (kMvPad * wl) / 16; j <= (kMvPad * wl + kMvPad - 1) / 16; j++)
+#pragma unroll
+               for (int rg = 0; rg < 4; rg++) {
+                  const int fj = 16 * j + lg + 4 * rg - kMvPad * wl;
+                  const double phi = (fj >= 0 && fj < kMvPad) ? As[fj * kMsLdA + wm + lr] : 0.0;
+                  psum = fma(acc[j][rg], phi, psum);
+               }
+         }
+      }
+   }
+   __syncthreads();
+   double* s_q = m_smem + kMvPad * kMsLdA;  // [point]
+   {
+      const double v0 = __shfl(psum, lr), v1 = __shfl(psum, lr + 16), v2 = __shfl(psum, lr + 32),
+                   v3 = __shfl(psum, lr + 48);
+      if (lg == 0) s_q[wm + lr] = ((v0 + v1) + v2) + v3;
+   }
+   __syncthreads();
+   bool outside = false;
+   if (part == 0 && live) {
+      for (int c = 0; c < nw; c++) {
+         const double xs = (X[(size_t)feature[c] * (size_t)ldim + ip] - centre[c]) * scale[c];
+         outside = outside || !(fabs(xs) <= kMpLimit);
+      }
+      out[ip] = outside ? __builtin_nan("") : sqrt(fabs(ff * (noise + s_q[p])));
+   }
+   if (cnt_out) {
+      const unsigned int cnt = (unsigned int)__popcll(__ballot(outside));
+      if (lane == 0) s_cnt[wave] = cnt;
+      __syncthreads();
+      if (tid == 0) {
+         unsigned int tsum = 0;
+         for (int w = 0; w < kMsThreads / kWave; w++) tsum += s_cnt[w];
+         cnt_out[blockIdx.x] = tsum;
+      }
+   }
+}
+
+int model_predict_std(Model* M, const double* Xnew, int n_new, long long ldim, double* std_out, int with_noise,
+                      long long* n_outside)
+{
+   hipStream_t s = current_stream();
+   const int nw = M->nw, Rp = mv_order(nw);
+   const bool odev = is_device_ptr(std_out);
+   double *xown = nullptr, *oown = nullptr;
+   const double ff = M->f * M->f, noise = with_noise ? M->mu : 0.0;
+   auto body = [&]() -> int {
+      const double* dX;
+      long long ld;
+      if (stage_points(M, Xnew, n_new, ldim, s, &dX, &ld, &xown)) return -1;
+      double* dout = std_out;
+      if (!odev) {
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&oown, sizeof(double) * (size_t)n_new));
+         dout = oown;
+      }
+      static const bool attr = []() {
+         (void)hipFuncSetAttribute((const void*)k_model_std, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMsLds);
+         (void)hipGetLastError();
+         return true;
+      }();
+      (void)attr;
+      const size_t nblk = ((size_t)n_new + kMsPts - 1) / kMsPts;
+      if (n_outside && grow_counts(M, nblk)) return -1;
+      hipLaunchKernelGGL(k_model_std, dim3((unsigned int)nblk), dim3(kMsThreads), kMsLds, s, (const double*)M->d_S, Rp,
+                         (const double*)M->d_centre, (const double*)M->d_scale, (const int*)M->d_feature, nw, dX, ld,
+                         n_new, ff, noise, dout, n_outside ? M->d_cnt : (unsigned int*)nullptr);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (!odev)
+         NFFT4GP_HIP_CHECK(hipMemcpyAsync(std_out, oown, sizeof(double) * (size_t)n_new, hipMemcpyDeviceToHost, s));
+      if (n_outside) {
+         if (read_counts(M, nblk, s, n_outside)) return -1;
+      } else if (xown || oown) {
+         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      }
+      return 0;
+   };
+   const int rc = body();
+   if (xown || oown) (void)hipStreamSynchronize(s);
+   for (double* p : {xown, oown})
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
 }  // namespace
 }  // namespace nfft4gp_amd
 
@@ -372,6 +838,92 @@ int Nfft4GPAmdModelCoefficients(void* model, double* H, double* centre, double* 
       if (scale) scale[c] = M->scale[c];
       if (feature) feature[c] = M->feature[c];
    }
+   return 0;
+}
+
+int Nfft4GPAmdModelFeatureWeights(int kernel, double l, double scale, int nw, double* w33)
+{
+   if ((kernel != 0 && kernel != 1) || !(l > 0.0) || !(scale > 0.0) || nw < 1 || !w33) return -1;
+   feature_weights(kernel, l, scale, nw, w33);
+   return 0;
+}
+
+static bool variance_fits(const Model* M, const char* who)
+{
+   if (M->nw <= kMvMaxNw) return true;
+   fprintf(stderr, "nfft4gp_amd: %s: the variance matrix of %d windows would take %.0f MB; the limit is %d windows "
+                   "(170 MB).\n", who, M->nw, 8e-6 * kMvPad * kMvPad * (double)M->nw * M->nw, kMvMaxNw);
+   return false;
+}
+
+int Nfft4GPAmdModelFitVariance(void* model, const double* X, int n, int ldim, int d)
+{
+   Model* M = (Model*)model;
+   if (!M || !X || d != M->d || n < 1 || ldim < n) return -1;
+   if (!variance_fits(M, "Nfft4GPAmdModelFitVariance")) return -1;
+   return model_fit_variance(M, X, n, (long long)ldim);
+}
+
+int Nfft4GPAmdModelPredictStd(void* model, const double* Xnew, int n_new, int ldim, int d, double* std_out,
+                              int with_noise, long long* n_outside)
+{
+   Model* M = (Model*)model;
+   if (!M || d != M->d || n_new < 0 || ldim < n_new) return -1;
+   if (!M->d_S) return -3;
+   if (n_outside) *n_outside = 0;
+   if (n_new == 0) return 0;
+   if (!Xnew || !std_out) return -1;
+   return model_predict_std(M, Xnew, n_new, (long long)ldim, std_out, with_noise, n_outside);
+}
+
+int Nfft4GPAmdModelVarianceInfo(void* model, int* R)
+{
+   Model* M = (Model*)model;
+   if (!M) return -1;
+   if (R) *R = M->R;
+   return 0;
+}
+
+int Nfft4GPAmdModelFitTimes(void* model, double* ms3)
+{
+   Model* M = (Model*)model;
+   if (!M || !ms3) return -1;
+   for (int i = 0; i < 3; i++) ms3[i] = M->fit_ms[i];
+   return 0;
+}
+
+int Nfft4GPAmdModelVariance(void* model, double* S)
+{
+   Model* M = (Model*)model;
+   if (!M || !S) return -1;
+   if (!M->d_S) return -3;
+   const int Rp = mv_order(M->nw), R = M->R;
+   std::vector<double> h((size_t)Rp * Rp);
+   NFFT4GP_HIP_CHECK(hipMemcpy(h.data(), M->d_S, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+   for (int i = 0; i < R; i++)
+      for (int j = 0; j < R; j++)
+         S[(size_t)i * R + j] = h[(size_t)(i / kMvFeat * kMvPad + i % kMvFeat) * Rp + j / kMvFeat * kMvPad + j % kMvFeat];
+   return 0;
+}
+
+int Nfft4GPAmdModelSetVariance(void* model, const double* S, int R)
+{
+   Model* M = (Model*)model;
+   if (!M || !S || R != kMvFeat * M->nw) return -1;
+   if (!variance_fits(M, "Nfft4GPAmdModelSetVariance")) return -1;
+   const int Rp = mv_order(M->nw);
+   std::vector<double> h((size_t)Rp * Rp, 0.0);
+   for (int i = 0; i < R; i++)
+      for (int j = 0; j < R; j++)
+         h[(size_t)(i / kMvFeat * kMvPad + i % kMvFeat) * Rp + j / kMvFeat * kMvPad + j % kMvFeat] = S[(size_t)i * R + j];
+   double* dS = nullptr;
+   if (to_device(&dS, h.data(), h.size())) {
+      if (dS) (void)hipFree(dS);
+      return -1;
+   }
+   if (M->d_S) (void)hipFree(M->d_S);
+   M->d_S = dS;
+   M->R = R;
    return 0;
 }
 

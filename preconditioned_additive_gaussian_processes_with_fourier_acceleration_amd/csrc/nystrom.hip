@@ -531,6 +531,8 @@ struct RocSolver {
    decltype(&rocsolver_dpotrf) potrf = nullptr;
    decltype(&rocsolver_dtrtri) trtri = nullptr;
    decltype(&rocsolver_dsyevd) syevd = nullptr;
+   decltype(&rocsolver_dgetrf) getrf = nullptr;  // optional: lu_solve_dev falls back to the host without them
+   decltype(&rocsolver_dgetrs) getrs = nullptr;
 };
 
 // first loadable of the given names, or nullptr with the dlerror of each attempt appended to `why`.  The
@@ -581,6 +583,8 @@ RocSolver& rocsolver()
       R.potrf = (decltype(&rocsolver_dpotrf))dlsym(hs, "rocsolver_dpotrf");
       R.trtri = (decltype(&rocsolver_dtrtri))dlsym(hs, "rocsolver_dtrtri");
       R.syevd = (decltype(&rocsolver_dsyevd))dlsym(hs, "rocsolver_dsyevd");
+      R.getrf = (decltype(&rocsolver_dgetrf))dlsym(hs, "rocsolver_dgetrf");
+      R.getrs = (decltype(&rocsolver_dgetrs))dlsym(hs, "rocsolver_dgetrs");
       if (!create || !R.set_stream || !R.potrf || !R.trtri || !R.syevd)
          why += "\n  a rocBLAS / rocSOLVER entry point is missing";
       else if (create(&R.h) != rocblas_status_success)
@@ -599,6 +603,17 @@ RocSolver& rocsolver()
          (void)R.trtri(R.h, rocblas_fill_lower, rocblas_diagonal_non_unit, 2, A, 2, info);
          (void)hipMemcpy(A, one, sizeof(one), hipMemcpyHostToDevice);
          (void)R.syevd(R.h, rocblas_evect_none, rocblas_fill_lower, 2, A, 2, A + 4, A + 6, info);
+         if (R.getrf && R.getrs) {
+            int* piv = nullptr;
+            if (hipMalloc((void**)&piv, sizeof(int) * 2) == hipSuccess) {
+               (void)hipMemcpy(A, one, sizeof(one), hipMemcpyHostToDevice);
+               (void)hipMemcpy(A + 4, one, sizeof(one), hipMemcpyHostToDevice);
+               (void)R.getrf(R.h, 2, 2, A, 2, piv, info);
+               (void)R.getrs(R.h, rocblas_operation_none, 2, 2, A, 2, piv, A + 4, 2);
+               (void)hipDeviceSynchronize();
+            }
+            (void)hipFree(piv);
+         }
          (void)hipDeviceSynchronize();
       }
       (void)hipFree(A);
@@ -663,6 +678,46 @@ int sym_eigvals_dev(double* A, int n, std::vector<double>& w, hipStream_t s)
    return sym_eig(h, n, w, V);
 }
 
+// B <- A^{-1} B by LU with partial pivoting (dgetrf / dgetrs semantics; A n x n and B n x nrhs column-major, A
+// overwritten by its factors); returns 0 or the first zero pivot's column + 1
+int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs)
+{
+   std::vector<int> piv(n);
+   for (int j = 0; j < n; j++) {
+      double* cj = A.data() + (size_t)j * n;
+      int p = j;
+      for (int i = j + 1; i < n; i++)
+         if (std::fabs(cj[i]) > std::fabs(cj[p])) p = i;
+      piv[j] = p;
+      if (cj[p] == 0.0) return j + 1;
+      if (p != j)
+         for (int c = 0; c < n; c++) std::swap(A[j + (size_t)c * n], A[p + (size_t)c * n]);
+      const double inv = 1.0 / cj[j];
+      for (int i = j + 1; i < n; i++) cj[i] *= inv;
+      for (int c = j + 1; c < n; c++) {  // right-looking update, one contiguous column at a time
+         double* cc = A.data() + (size_t)c * n;
+         const double u = cc[j];
+         if (u != 0.0)
+            for (int i = j + 1; i < n; i++) cc[i] -= cj[i] * u;
+      }
+   }
+   for (int c = 0; c < nrhs; c++) {
+      double* b = B.data() + (size_t)c * n;
+      for (int j = 0; j < n; j++) std::swap(b[j], b[piv[j]]);  // whole rows were interchanged: P first, then L
+      for (int j = 0; j < n; j++) {
+         const double v = b[j];
+         if (v != 0.0)
+            for (int i = j + 1; i < n; i++) b[i] -= A[i + (size_t)j * n] * v;
+      }
+      for (int j = n - 1; j >= 0; j--) {
+         const double v = (b[j] /= A[j + (size_t)j * n]);
+         if (v != 0.0)
+            for (int i = 0; i < j; i++) b[i] -= A[i + (size_t)j * n] * v;
+      }
+   }
+   return 0;
+}
+
 // L^{-1} of chol(A) (lower) in place; returns 0 or the failing column + 1
 int chol_inverse_host(std::vector<double>& A, int k)
 {
@@ -708,6 +763,41 @@ int chol_inverse_dev(double* A, int k, double shift, double* G, double* Gt, int*
    if (hipMemcpy(Gt, ht.data(), sizeof(double) * ht.size(), hipMemcpyHostToDevice)) return -1;
    if (G && hipMemcpy(G, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice)) return -1;
    return 0;
+}
+
+// X = A^{-1} B in place of B: A n x n general (overwritten by its LU), B n x nrhs, both column-major with leading
+// dimension n on the device.  rocSOLVER getrf / getrs when they loaded, otherwise a host LU with partial pivoting
+// (row interchanges, columns eliminated left to right: the same answer to rounding).  Returns 0, the first zero
+// pivot's column + 1 when A is singular, or -1.
+int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s)
+{
+   RocSolver& R = rocsolver();
+   if (R.ok && R.getrf && R.getrs) {
+      int *d_piv = nullptr, *d_info = nullptr;
+      int info = 0, rc = -1;
+      if (dalloc(&d_piv, n) == 0 && dalloc(&d_info, 1) == 0) {
+         R.set_stream(R.h, s);
+         if (R.getrf(R.h, n, n, A, n, d_piv, d_info) == rocblas_status_success &&
+             hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess) {
+            if (info)
+               rc = info;
+            else if (R.getrs(R.h, rocblas_operation_none, n, nrhs, A, n, d_piv, B, n) == rocblas_status_success &&
+                     hipStreamSynchronize(s) == hipSuccess)
+               rc = 0;
+         }
+      }
+      (void)hipFree(d_piv);
+      (void)hipFree(d_info);
+      return rc;
+   }
+   std::vector<double> a((size_t)n * n), b((size_t)n * nrhs);
+   if (hipMemcpyAsync(a.data(), A, sizeof(double) * a.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipMemcpyAsync(b.data(), B, sizeof(double) * b.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipStreamSynchronize(s) != hipSuccess)
+      return -1;
+   if (int info = lu_solve_host(a, n, b, nrhs)) return info;
+   return hipMemcpy(B, b.data(), sizeof(double) * b.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
 
 __global__ void k_zero_upper(double* A, int k)
@@ -1047,6 +1137,16 @@ extern "C" int Nfft4GPAmdHostCholInverse(const double* A, int k, double shift, d
    const int info = nfft4gp_amd::chol_inverse_host(a, k);
    if (info) return info;
    memcpy(G, a.data(), sizeof(double) * (size_t)k * k);
+   return 0;
+}
+
+extern "C" int Nfft4GPAmdHostLuSolve(const double* A, int n, double* B, int nrhs)
+{
+   if (!A || !B || n < 1 || nrhs < 0) return -1;
+   std::vector<double> a(A, A + (size_t)n * n), b(B, B + (size_t)n * nrhs);
+   const int info = nfft4gp_amd::lu_solve_host(a, n, b, nrhs);
+   if (info) return info;
+   memcpy(B, b.data(), sizeof(double) * b.size());
    return 0;
 }
 

@@ -195,10 +195,11 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
     return hyper, loss, gnorm, int(flag)
 
 
-def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None):
+def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None, variance=False):
     """The fitted model at the hyperparameters ``hyper`` = (f, l, mu) before the transform: sets the kernel up
     (Gaussian, or the kernel ``op`` was last set up with), solves f^2 (K + mu I) alpha = y with FGMRES on the
-    device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse."""
+    device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse.
+    ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works."""
     import torch
 
     from .solvers import fgmres
@@ -223,4 +224,7 @@ def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, tra
         raise RuntimeError("the kernel setup failed")
     b = torch.as_tensor(np.ascontiguousarray(np.asarray(y, dtype=np.float64)), device="cuda")
     alpha = fgmres(op, b, kdim=int(maxits), maxits=int(maxits), tol=float(tol))[0]
-    return FittedModel.from_operator(op, alpha)
+    model = FittedModel.from_operator(op, alpha)
+    if variance:
+        model.fit_variance(X)
+    return model

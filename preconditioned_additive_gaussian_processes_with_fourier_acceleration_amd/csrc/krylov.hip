@@ -1024,9 +1024,21 @@ struct Ctx {
    {
       *grid = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
       if (comm || g_k.ensure_chain()) return -1;
-      if ((size_t)*grid * 4096 >= n && (int)*grid <= g_k.chain_occ) return 0;
       const char* e = getenv("NFFT4GP_AMD_MGS_WIDE");
-      if (e && atoi(e) == 0) return -1;
+      const int forced = e ? atoi(e) : 0;
+      // NFFT4GP_AMD_MGS_WIDE=S (one of kWideS): that S at any n its resident grid covers in S passes, ahead of
+      // k_mgs_chain (the tests run every instantiation at small n this way)
+      for (int x = 0; x < 6; x++)
+         if (forced == kWideS[x]) {
+            const size_t per = (size_t)kWideS[x] * 4096;
+            const size_t g = (n + per - 1) / per;
+            if (g >= 1 && g <= (size_t)g_k.wide_occ[x] && g <= (size_t)kKMaxBlocks) {
+               *grid = (unsigned)g;
+               return kWideS[x];
+            }
+         }
+      if ((size_t)*grid * 4096 >= n && (int)*grid <= g_k.chain_occ) return 0;
+      if (e && forced == 0) return -1;
       for (int x = 0; x < 6; x++) {
          const size_t per = (size_t)kWideS[x] * 4096;
          const size_t g = (n + per - 1) / per;
@@ -2692,6 +2704,76 @@ extern "C" int Nfft4GPAmdDebugChainFault(int mode)
    *g_k.hchain_err = 0;
    g_k.chain_off = false;
    return was_off;
+}
+
+// One orthogonalisation sweep through the solvers' own launch code (Ctx, comm == NULL, the library's stream) for
+// tests/test_gpu_krylov_kernels.py.  w (n), V, Z (m columns of n): device.  kind:
+//   0  the per-projection MGS chain as FGMRES's fallback makes it (Ctx::gs on mgs_form's grid): h_out[0..m]
+//   1  Ctx::mgs_chain (k_mgs_chain / k_mgs_wide<S>): h_out[0..m]; returns 1, nothing run, where it declines
+//   2  Ctx::block_gs(w, V, Z, m, h, with_norm): h_out[0..m + 1]
+//   3  Ctx::block_cgs2(w, V, m, h): h_out[0..2m + 3]
+//   4  Ctx::lanczos_local(w, V, Z, m, h): h_out[0..m + 1]
+// m = 0 (kinds 0, 1): the norm only.  h_out: host.  info (host, 6 ints): [0] the MGS form (0 k_mgs_chain, S
+// k_mgs_wide<S>, -1 per projection), [1] its grid, [2] bd_vec, [3] the folded reduce, [4] k_lanczos_local
+// launched, [5] the one-launch kernels' error word as read back (a set word is handled as the solvers do).
+extern "C" int Nfft4GPAmdDebugOrthoSweep(int kind, double* w, const double* V, const double* Z, long long n, int m,
+                                         int with_norm, double* h_out, int* info)
+{
+   if (!need_device("Nfft4GPAmdDebugOrthoSweep") || n <= 0 || m < 0 || 2 * m + 4 > KScratch::kScal || !w || !h_out ||
+       !info || g_k.ensure_chain())
+      return -1;
+   Ctx c{current_stream(), (size_t)n, nullptr};
+   double* hd = g_k.scal;
+   const size_t nn = (size_t)n;
+   for (int q = 0; q < 6; q++) info[q] = 0;
+   int count = 0;
+   bool one_launch = false;
+   if (kind == 0 || kind == 1) {
+      unsigned mg = 0;
+      const int form = c.mgs_form(&mg);
+      info[0] = form;
+      info[1] = (int)mg;
+      count = m + 1;
+      if (kind == 1) {
+         const int rc = c.mgs_chain(w, V, m, hd);
+         if (rc) return rc;
+         one_launch = true;
+      } else {
+         info[0] = -1;
+         if (form < 0) mg = 0;
+         for (int j = 0; j < m; j++)
+            if (c.gs(w, j ? V + (size_t)(j - 1) * nn : nullptr, j ? hd + j - 1 : nullptr, V + (size_t)j * nn, hd + j, mg))
+               return -1;
+         if (c.gs(w, m ? V + (size_t)(m - 1) * nn : nullptr, m ? hd + m - 1 : nullptr, nullptr, hd + m, mg)) return -1;
+      }
+   } else if (kind == 2) {
+      info[2] = c.bd_vec(w, V, Z) ? 1 : 0;
+      info[3] = Ctx::fold_reduce() ? 1 : 0;
+      count = m + 2;
+      if (c.block_gs(w, V, Z, m, hd, with_norm)) return -1;
+   } else if (kind == 3) {
+      info[2] = c.bd_vec(w, V, V) ? 1 : 0;
+      info[3] = Ctx::fold_reduce() ? 1 : 0;
+      count = 2 * m + 4;
+      if (c.block_cgs2(w, V, m, hd)) return -1;
+   } else if (kind == 4) {
+      count = m + 2;
+      if (c.lanczos_local(w, V, Z, m, hd)) return -1;
+      info[4] = c.lz_launched ? 1 : 0;
+      one_launch = c.lz_launched;
+      if (!c.lz_launched) {
+         info[2] = c.bd_vec(w, V, Z) ? 1 : 0;
+         info[3] = Ctx::fold_reduce() ? 1 : 0;
+      }
+   } else {
+      return -1;
+   }
+   if (c.read(hd, count, h_out)) return -1;
+   if (one_launch) {
+      info[5] = *g_k.hchain_err;
+      if (kind == 1 ? c.chain_failed() : c.lanczos_local_failed()) return -2;
+   }
+   return 0;
 }
 
 // Timing probe for tools/reorth_probe.py: `reps` classical Gram-Schmidt passes (Ctx::block_gs, the Lanczos

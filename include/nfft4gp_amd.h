@@ -901,7 +901,58 @@ int Nfft4GPAmdModelSetVariance(void *model, const NFFT4GP_DOUBLE *S, int R);
  * the kernel's Fourier coefficients at the window's sigma (index k + 16, k = -16..15):
  * w[cos 0] = b^_0 / nw; w[cos k] = w[sin k] = 2 b^_k / nw, k = 1..15; w[cos 16] = w[sin 16] = b^_-16 / nw */
 int Nfft4GPAmdModelFeatureWeights(int kernel, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE scale, int nw, NFFT4GP_DOUBLE *w33);
+/* its twin: dw33 = dW/dl, the same map of the derivative kernel's b^ (kind 1 / 3 at the window's sigma) times
+ * dscale (Gaussian 2 scale sqrt 2 / sigma, Matern-1/2 scale / sigma): f^2 Z diag(dw) Z^T is the l block of the
+ * gradient matvec.  Host only. */
+int Nfft4GPAmdModelFeatureWeightsGrad(int kernel, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE scale, int nw,
+                                      NFFT4GP_DOUBLE *dw33);
 void Nfft4GPAmdModelFree(void *model);
+
+/* ---- the exact GP loss, gradient, solve and variance matrix in feature space -------------------
+ * With 1-D windows A = f^2 (Z W Z^T + mu I) and only W depends on the hyperparameters, so G = Z^T Z, b = Z^T y
+ * and y^T y are formed once per data set; every loss, gradient, solve and S after that is R x R work (R = 33 nw):
+ * one LU of B = mu I + W G and one solve for B^{-1} per evaluation, no Krylov iteration, no probe vectors and no
+ * pass over the n points.  The loss and all three gradient components are those of Nfft4GPGpLoss with the
+ * log-determinant and the traces exact for this operator (which carries the NFFT's truncation against the true
+ * kernel exactly as the matvec does).
+ * Nfft4GPAmdFeatureGpCreate: additive_handle as for Nfft4GPAmdModelCreate (whole, set up, one feature per window,
+ * at most 128 windows); X (n x d column-major, ldim >= n) the handle's data and y (n), host or device.  Takes the
+ * handle's centres, scales, features and kernel kind; holds G, b, y^T y and n, not X.  Deterministic: two creates
+ * give the same bits.  NULL (message on stderr) when the handle is refused, n is not the handle's n, or a row of X
+ * lies outside the handle's domain (X is then not the handle's data; the count is printed). */
+void *Nfft4GPAmdFeatureGpCreate(void *additive_handle, const NFFT4GP_DOUBLE *X, int n, int ldim, int d,
+                                const NFFT4GP_DOUBLE *y);
+/* the transform of the hyperparameters (default softplus) and the gradient mask (3 ints, 0 = that component is
+ * returned as 0; NULL: none) of Nfft4GPAmdFeatureGpLoss */
+int Nfft4GPAmdFeatureGpSetOptions(void *fgp, nfft4gp_transform_type transform, const int *mask);
+/* a func_loss: x = (f, l, mu) before the transform; *lossp = 1/2 (y^T A^{-1} y / n + log|det A| / n + log 2 pi) and
+ * dloss[3] its gradient in x.  Nfft4GPOptimizationAdamSetProblem(adam, &Nfft4GPAmdFeatureGpLoss, fgp, 3) trains on
+ * it.  -1 when mu <= 0 or l <= 0 after the transform, a pivot of B is zero, or a result is not finite.  A is not
+ * always definite (W has negative entries): the loss uses log|det B| and Nfft4GPAmdFeatureGpStatus reports the sign. */
+int Nfft4GPAmdFeatureGpLoss(void *fgp, NFFT4GP_DOUBLE *x, NFFT4GP_DOUBLE *lossp, NFFT4GP_DOUBLE *dloss);
+/* alpha (n, host or device) = A^{-1} y = (y - Z v) / (f^2 mu) at the transformed hyperparameters (f, l, mu); X and y
+ * are the data of the create call (the object does not hold them).  -2 when a row of X is outside the domain. */
+int Nfft4GPAmdFeatureGpSolve(void *fgp, const NFFT4GP_DOUBLE *X, int n, int ldim, int d, const NFFT4GP_DOUBLE *y,
+                             NFFT4GP_DOUBLE f, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE mu, NFFT4GP_DOUBLE *alpha);
+/* the same for any right-hand side r (n, host or device): one more pass over X forms Z^T r (no Gram), then
+ * alpha = (r - Z B^{-1} (w o Z^T r)) / (f^2 mu).  FeatureGP.model uses it for one step of iterative refinement
+ * against the operator's own matvec. */
+int Nfft4GPAmdFeatureGpSolveRhs(void *fgp, const NFFT4GP_DOUBLE *X, int n, int ldim, int d, const NFFT4GP_DOUBLE *r,
+                                NFFT4GP_DOUBLE f, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE mu, NFFT4GP_DOUBLE *alpha);
+/* S = mu B^{-1} W symmetrised, R x R row-major unpadded (host or device): the layout of Nfft4GPAmdModelVariance /
+ * Nfft4GPAmdModelSetVariance */
+int Nfft4GPAmdFeatureGpVariance(void *fgp, NFFT4GP_DOUBLE f, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE mu, NFFT4GP_DOUBLE *S);
+/* the posterior mean phi*^T (w o u) at the n_new rows of Xnew, with the conventions of Nfft4GPAmdModelPredict
+ * (host or device, NaN and *n_outside for points outside the domain, bits independent of the batching) */
+int Nfft4GPAmdFeatureGpPredict(void *fgp, NFFT4GP_DOUBLE f, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE mu,
+                               const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, NFFT4GP_DOUBLE *mean,
+                               long long *n_outside);
+/* G (R x R row-major), b (R) and *yy to the host, unpadded; any output may be NULL */
+int Nfft4GPAmdFeatureGpMoments(void *fgp, NFFT4GP_DOUBLE *G, NFFT4GP_DOUBLE *b, NFFT4GP_DOUBLE *yy);
+int Nfft4GPAmdFeatureGpInfo(void *fgp, int *n, int *nw, int *R, int *kernel);
+/* the last evaluation's sign of det B (+1 / -1; 0: none yet, or it failed) and log|det B| */
+int Nfft4GPAmdFeatureGpStatus(void *fgp, int *det_sign, NFFT4GP_DOUBLE *logabsdet);
+void Nfft4GPAmdFeatureGpFree(void *fgp);
 
 /* ---- host-only helpers (no GPU needed): the setup math of the device plan, exported so the CPU
  * test-suite can check it and emulate the kernels against the oracle ------------------------------- */
@@ -938,6 +989,9 @@ int Nfft4GPAmdHostCholInverse(const NFFT4GP_DOUBLE *A, int k, NFFT4GP_DOUBLE shi
 /* the host fallback of the model variance's LU (used when rocSOLVER cannot be loaded): B <- A^{-1} B by LU with
  * partial pivoting, A n x n general, B n x nrhs, column-major; 0, the first zero pivot's column + 1, or -1 */
 int Nfft4GPAmdHostLuSolve(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *B, int nrhs);
+/* the same LU's log|det A| (U's diagonal summed in column order) and the sign of det A; 0, the first zero pivot's
+ * column + 1, or -1 */
+int Nfft4GPAmdHostLuLogdet(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *logabsdet, int *sign);
 
 #ifdef __cplusplus
 }

@@ -278,6 +278,22 @@ _SIGS = {
     "Nfft4GPAmdModelSetVariance": (C.c_int, [vp, vp, C.c_int]),
     "Nfft4GPAmdModelFeatureWeights": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
     "Nfft4GPAmdModelFree": (None, [vp]),
+    "Nfft4GPAmdModelFeatureWeightsGrad": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
+    "Nfft4GPAmdFeatureGpCreate": (vp, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "Nfft4GPAmdFeatureGpSetOptions": (C.c_int, [vp, C.c_int, vp]),
+    "Nfft4GPAmdFeatureGpLoss": (C.c_int, [vp, vp, vp, vp]),
+    "Nfft4GPAmdFeatureGpSolve": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
+                                           vp]),
+    "Nfft4GPAmdFeatureGpSolveRhs": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double,
+                                              C.c_double, vp]),
+    "Nfft4GPAmdFeatureGpVariance": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, vp]),
+    "Nfft4GPAmdFeatureGpPredict": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, vp, C.c_int, C.c_int, C.c_int, vp,
+                                             C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdFeatureGpMoments": (C.c_int, [vp, vp, vp, dp]),
+    "Nfft4GPAmdFeatureGpInfo": (C.c_int, [vp, ip, ip, ip, ip]),
+    "Nfft4GPAmdFeatureGpStatus": (C.c_int, [vp, ip, dp]),
+    "Nfft4GPAmdFeatureGpFree": (None, [vp]),
+    "Nfft4GPAmdHostLuLogdet": (C.c_int, [vp, C.c_int, dp, ip]),
     "Nfft4GPAmdHostTapPoly": (C.c_int, [vp]),
     "Nfft4GPAmdHostCirculant": (C.c_int, [C.c_int, C.c_double, C.c_double, vp, vp]),
     "Nfft4GPAmdHostPrepare": (C.c_double, [vp, C.c_int, vp]),

@@ -1,0 +1,635 @@
+// feature_gp.hip -- the exact GP loss, its gradient, the solve and the variance matrix in feature space.
+//
+// With 1-D windows the operator is A = f^2 (Z W Z^T + mu I) (model.hip, "the predictive variance"): Z holds 33
+// trigonometric features per window of the window's quantised coordinate and W is diagonal.  A handle's centres and
+// scales are fixed at its first setup, so only W depends on the hyperparameters: G = Z^T Z, b = Z^T y and y^T y are
+// formed once per data set (window_moments) and everything after is R x R work, R = 33 nw.  With
+//   B = mu I + W G,  v = B^{-1} (w o b),  u = (b - G v) / mu = Z^T M^{-1} y,  M = Z W Z^T + mu I
+//   q = (y^T y - b^T v) / mu = y^T M^{-1} y,   |M^{-1} y|^2 = (y^T y - 2 v^T b + v^T G v) / mu^2
+//   log det A = n log f^2 + (n - R) log mu + log |det B|                       (Sylvester; n < R too)
+// the reference's loss (gp_loss.c:224-283) is  1/2 (q / (f^2 n) + log det A / n + log 2 pi)  and its gradient
+// 1/2 (-L1_i + L2_i) dt_i with
+//   n L1 = 2 q / f^3,  u^T (w' o u) / f^2,  |M^{-1} y|^2 / f^2            (f, l, mu)
+//   n L2 = 2 n / f,    tr(B^{-1} diag(w') G),  (n - R) / mu + tr(B^{-1})
+// w' = dW/dl (feature_weights_grad).  alpha = (y - Z v) / (f^2 mu) solves A alpha = y, S = mu B^{-1} W symmetrised
+// is the matrix of Nfft4GPAmdModelFitVariance, and the posterior mean at a point with features phi is phi^T (w o u).
+// W has negative entries, so B is factored by LU; the loss uses log |det B| and the sign of det B is only reported.
+// Internally the slots are padded as in model.hip (36 per window, windows to a multiple of 4): a padded slot has
+// zero weight and zero features, B keeps mu on its diagonal there, and (R_p - R) log mu leaves the factor's
+// log-determinant again.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "internal.h"
+
+namespace nfft4gp_amd {
+namespace {
+
+constexpr int kFaThreads = 256;
+constexpr int kFaPts = 4;  // points per thread, strided by the workgroup (coalesced columns, 4 independent chains)
+constexpr int kFsThreads = 256;
+
+struct FeatureGp {
+   int n = 0, nw = 0, d = 0, kernel = 0, Rp = 0, R = 0;
+   std::vector<double> scale;   // host copy (the weights are formed on the host: 33 nw values)
+   double* d_centre = nullptr;  // [nw]
+   double* d_scale = nullptr;   // [nw]
+   int* d_feature = nullptr;    // [nw]
+   double* d_G = nullptr;       // [R_p][R_p] Z^T Z
+   double* d_by = nullptr;      // [R_p] Z^T y, then y^T y
+   double yy = 0.0;
+   int transform = 0;
+   bool has_mask = false;
+   int mask[3] = {1, 1, 1};
+   // the last evaluation
+   int det_sign = 0;
+   double logabsdet = 0.0;
+   bool factored = false;  // d_Binv and d_vec hold the quantities of (fl, fmu)
+   double fl = 0.0, fmu = 0.0;
+   double sc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // b^T v, v^T G v, u^T (w' o u), tr B^{-1}, tr(B^{-1} diag(w') G)
+   // scratch of an evaluation
+   double* d_B = nullptr;     // [R_p][R_p] mu I + W G, then its factors
+   double* d_Binv = nullptr;  // [R_p][R_p + 1] B^{-1}, then v = B^{-1} (w o b): one solve, R_p + 1 right-hand sides
+   int* d_piv = nullptr;      // the factorisation's row interchanges (further right-hand sides: lu_resolve_dev)
+   double* d_vec = nullptr;   // [7][R_p]: w, w', v, G v, w o u, column sums of the trace, 8 scalars
+   unsigned int* d_cnt = nullptr;
+   size_t cnt_cap = 0;
+};
+enum { kVw = 0, kVdw, kVv, kVgv, kVwu, kVpart, kVscal };
+
+void fgp_free(FeatureGp* F)
+{
+   if (!F) return;
+   for (void* p : {(void*)F->d_centre, (void*)F->d_scale, (void*)F->d_feature, (void*)F->d_G, (void*)F->d_by,
+                   (void*)F->d_B, (void*)F->d_Binv, (void*)F->d_piv, (void*)F->d_vec, (void*)F->d_cnt})
+      if (p) (void)hipFree(p);
+   delete F;
+}
+
+// B = mu I + W G and the right-hand sides [I | w o b] of its solve (rhs: column R_p of Binv)
+__global__ void k_fgp_system(const double* __restrict__ G, const double* __restrict__ w, const double* __restrict__ b,
+                             int Rp, double mu, double* __restrict__ B, double* __restrict__ Binv,
+                             double* __restrict__ rhs)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i >= Rp) return;
+   const size_t e = i + (size_t)j * Rp;
+   B[e] = w[i] * G[e] + (i == j ? mu : 0.0);
+   Binv[e] = (i == j) ? 1.0 : 0.0;
+   if (j == 0) rhs[i] = w[i] * b[i];
+}
+
+__global__ void k_fgp_hadamard(const double* __restrict__ w, const double* __restrict__ b, int Rp,
+                               double* __restrict__ out)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i < Rp) out[i] = w[i] * b[i];
+}
+
+// the workgroup's sum of v over its threads in a fixed tree; every thread returns it
+__device__ inline double fgp_block_sum(double v, double* s_red)
+{
+   const int t = threadIdx.x;
+   __syncthreads();  // the previous sum's readers are done
+   s_red[t] = v;
+   __syncthreads();
+   for (int h = kFsThreads / 2; h > 0; h >>= 1) {
+      if (t < h) s_red[t] += s_red[t + h];
+      __syncthreads();
+   }
+   return s_red[0];
+}
+
+// part[j] = w'_j sum_i Binv(i, j) G(i, j): column j's share of tr(B^{-1} diag(w') G) (G is symmetric); one workgroup
+// per column, a thread adds its rows in order
+__global__ __launch_bounds__(kFsThreads) void k_fgp_trace_cols(const double* __restrict__ Binv,
+                                                               const double* __restrict__ G,
+                                                               const double* __restrict__ dw, int Rp,
+                                                               double* __restrict__ part)
+{
+   __shared__ double s_red[kFsThreads];
+   const int j = blockIdx.x;
+   const double* bc = Binv + (size_t)j * Rp;
+   const double* gc = G + (size_t)j * Rp;
+   double acc = 0.0;
+   for (int i = threadIdx.x; i < Rp; i += kFsThreads) acc = fma(bc[i], gc[i], acc);
+   const double t = fgp_block_sum(acc, s_red);
+   if (threadIdx.x == 0) part[j] = dw[j] * t;
+}
+
+// One workgroup: wu = w o u with u = (b - G v) / mu, and the five scalars of an evaluation, each one fixed-order
+// reduction over the slots: out = b^T v, v^T G v, u^T (w' o u), tr B^{-1} over the real slots, sum of part
+__global__ __launch_bounds__(kFsThreads) void k_fgp_scalars(const double* __restrict__ b, const double* __restrict__ w,
+                                                            const double* __restrict__ dw,
+                                                            const double* __restrict__ v, const double* __restrict__ Gv,
+                                                            const double* __restrict__ Binv,
+                                                            const double* __restrict__ part, int Rp, int nw, double mu,
+                                                            double* __restrict__ wu, double* __restrict__ out)
+{
+   __shared__ double s_red[kFsThreads];
+   double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+   for (int i = threadIdx.x; i < Rp; i += kFsThreads) {
+      const double u = (b[i] - Gv[i]) / mu;
+      wu[i] = w[i] * u;
+      a[0] = fma(b[i], v[i], a[0]);
+      a[1] = fma(v[i], Gv[i], a[1]);
+      a[2] = fma(dw[i] * u, u, a[2]);
+      const bool real = (i % kMvPad) < kMvFeat && (i / kMvPad) < nw;  // a padded slot's 1 / mu is not part of tr B^{-1}
+      if (real) a[3] += Binv[i + (size_t)i * Rp];
+      a[4] += part[i];
+   }
+   for (int k = 0; k < 5; k++) {
+      const double t = fgp_block_sum(a[k], s_red);
+      if (threadIdx.x == 0) out[k] = t;
+   }
+}
+
+// S (R x R row-major, unpadded) = mu B^{-1} W symmetrised
+__global__ void k_fgp_variance(const double* __restrict__ Binv, const double* __restrict__ w, int Rp, int R, double mu,
+                               double* __restrict__ S)
+{
+   const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+   if (j >= R) return;
+   const int ip = i / kMvFeat * kMvPad + i % kMvFeat, jp = j / kMvFeat * kMvPad + j % kMvFeat;
+   S[(size_t)i * R + j] = 0.5 * (mu * Binv[ip + (size_t)jp * Rp] * w[jp] + mu * Binv[jp + (size_t)ip * Rp] * w[ip]);
+}
+
+// out = a y + c (Z coef) over n points (y may be NULL: out = c (Z coef)).  One thread owns kFaPts points, strided by
+// the workgroup as in k_model_predict; the R_p coefficients sit in LDS (<= 36.9 KB at 128 windows, 9.2 KB at 32: 8
+// workgroups of 4 waves fill a CU's wave slots at 74 KB of its 160 KB) and every lane of a wave reads the same
+// address at the same time: a broadcast, no bank conflict.  Per (point, window): one coalesced coordinate load,
+// mv_angle, 16 mv_rotate steps and 33 FMAs -- about 170 flops per 8 bytes read, so the kernel is bound by the vector
+// fp64 rate and the 4 points per thread are its independent dependency chains.  A point's windows are added in
+// the order c = 0 .. nw - 1 by its own thread: no atomics, the same bits however the points are batched and
+// wherever the arrays came from.  A point outside a window's domain is NaN and counted (cnt_out may be NULL).
+__global__ __launch_bounds__(kFaThreads) void k_fgp_apply(const double* __restrict__ coef, int Rp,
+                                                          const double* __restrict__ centre,
+                                                          const double* __restrict__ scale,
+                                                          const int* __restrict__ feature, int nw,
+                                                          const double* __restrict__ X, long long ldim, int n,
+                                                          const double* __restrict__ y, double a, double c,
+                                                          double* __restrict__ out, unsigned int* __restrict__ cnt_out)
+{
+   extern __shared__ double f_coef[];
+   __shared__ unsigned int s_cnt[kFaThreads / kWave];
+   const int tid = threadIdx.x;
+   for (int i = tid; i < Rp; i += kFaThreads) f_coef[i] = coef[i];
+   __syncthreads();
+   const long long base = (long long)blockIdx.x * (kFaThreads * kFaPts) + tid;
+   double acc[kFaPts];
+   bool outside[kFaPts];
+#pragma unroll
+   for (int p = 0; p < kFaPts; p++) {
+      acc[p] = 0.0;
+      outside[p] = false;
+   }
+   for (int w = 0; w < nw; w++) {
+      const double ctr = centre[w], sc = scale[w];
+      const double* col = X + (size_t)feature[w] * (size_t)ldim;
+      const double* cf = f_coef + w * kMvPad;
+      double c1[kFaPts], s1[kFaPts], ck[kFaPts], sk[kFaPts];
+#pragma unroll
+      for (int p = 0; p < kFaPts; p++) {
+         const long long i = base + (long long)p * kFaThreads;
+         const double xv = (i < n) ? col[i] : ctr;
+         outside[p] = !mv_angle(xv, ctr, sc, c1[p], s1[p]) || outside[p];
+         acc[p] = fma(cf[0], 1.0, acc[p]);  // k = 0: cos 0
+         ck[p] = c1[p];
+         sk[p] = s1[p];
+      }
+#pragma unroll
+      for (int k = 1; k <= 16; k++) {
+         const double cc = cf[k], cs = cf[16 + k];
+#pragma unroll
+         for (int p = 0; p < kFaPts; p++) {
+            acc[p] = fma(cc, ck[p], acc[p]);
+            acc[p] = fma(cs, sk[p], acc[p]);
+            if (k < 16) mv_rotate(ck[p], sk[p], c1[p], s1[p]);
+         }
+      }
+   }
+   unsigned int cnt = 0;
+#pragma unroll
+   for (int p = 0; p < kFaPts; p++) {
+      const long long i = base + (long long)p * kFaThreads;
+      const bool live = i < n;
+      if (live) {
+         const double zc = c * acc[p];
+         out[i] = outside[p] ? __builtin_nan("") : (y ? fma(a, y[i], zc) : zc);
+      }
+      cnt += (unsigned int)__popcll(__ballot(live && outside[p]));
+   }
+   if (cnt_out) {
+      if ((tid & (kWave - 1)) == 0) s_cnt[tid / kWave] = cnt;
+      __syncthreads();
+      if (tid == 0) {
+         unsigned int t = 0;
+         for (int v = 0; v < kFaThreads / kWave; v++) t += s_cnt[v];
+         cnt_out[blockIdx.x] = t;
+      }
+   }
+}
+
+// a host or device array of rows x cols doubles (leading dimension ld) as a packed device array
+int stage(const double* src, size_t rows, size_t cols, size_t ld, hipStream_t s, const double** dev, long long* dld,
+          double** owned)
+{
+   *owned = nullptr;
+   *dev = src;
+   *dld = (long long)ld;
+   if (is_device_ptr(src)) return 0;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)owned, sizeof(double) * std::max<size_t>(1, rows * cols)));
+   NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(*owned, sizeof(double) * rows, src, sizeof(double) * ld, sizeof(double) * rows,
+                                      cols, hipMemcpyHostToDevice, s));
+   *dev = *owned;
+   *dld = (long long)rows;
+   return 0;
+}
+
+WindowMap window_map(const FeatureGp* F) { return WindowMap{F->nw, F->d, F->d_centre, F->d_scale, F->d_feature}; }
+
+// B^{-1}, v, G v, w o u and the scalars at (l, mu); kept until other hyperparameters are asked for.  0, -1 (bad
+// hyperparameters, a zero pivot, a HIP error)
+int fgp_factor(FeatureGp* F, double l, double mu)
+{
+   if (!(mu > 0.0) || !(l > 0.0) || !std::isfinite(mu) || !std::isfinite(l)) return -1;
+   if (F->factored && F->fl == l && F->fmu == mu) return 0;
+   F->factored = false;
+   F->det_sign = 0;
+   hipStream_t s = current_stream();
+   const int Rp = F->Rp, nw = F->nw;
+   const size_t rr = (size_t)Rp * Rp;
+   if (!F->d_B) {
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_B, sizeof(double) * rr));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_Binv, sizeof(double) * (rr + Rp)));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_piv, sizeof(int) * (size_t)Rp));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_vec, sizeof(double) * 7 * (size_t)Rp));
+   }
+   double* V = F->d_vec;
+   auto vec = [&](int which) { return V + (size_t)which * Rp; };
+   std::vector<double> w(2 * (size_t)Rp, 0.0);
+   for (int c = 0; c < nw; c++) {
+      feature_weights(F->kernel, l, F->scale[c], nw, w.data() + (size_t)c * kMvPad);
+      feature_weights_grad(F->kernel, l, F->scale[c], nw, w.data() + Rp + (size_t)c * kMvPad);
+   }
+   NFFT4GP_HIP_CHECK(hipMemcpyAsync(vec(kVw), w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, s));
+   NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));  // w leaves scope; the copy from pageable memory has been staged
+   hipLaunchKernelGGL(k_fgp_system, dim3((Rp + 255) / 256, Rp), dim3(256), 0, s, (const double*)F->d_G,
+                      (const double*)vec(kVw), (const double*)F->d_by, Rp, mu, F->d_B, F->d_Binv, F->d_Binv + rr);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   double lad = 0.0;
+   int sign = 0;
+   // v comes out of the factors' own substitution (backward stable), not from the explicit inverse: alpha's
+   // residual would otherwise carry cond(B) / mu
+   if (const int info = lu_solve_dev(F->d_B, Rp, F->d_Binv, Rp + 1, s, &lad, &sign, F->d_piv)) {
+      if (info > 0) fprintf(stderr, "nfft4gp_amd: feature GP: mu I + W G has a zero pivot in column %d.\n", info);
+      return -1;
+   }
+   NFFT4GP_HIP_CHECK(hipMemcpyAsync(vec(kVv), F->d_Binv + rr, sizeof(double) * Rp, hipMemcpyDeviceToDevice, s));
+   if (gemm_f64(false, Rp, 1, Rp, F->d_G, Rp, vec(kVv), Rp, vec(kVgv), Rp, s)) return -1;
+   hipLaunchKernelGGL(k_fgp_trace_cols, dim3(Rp), dim3(kFsThreads), 0, s, (const double*)F->d_Binv,
+                      (const double*)F->d_G, (const double*)vec(kVdw), Rp, vec(kVpart));
+   hipLaunchKernelGGL(k_fgp_scalars, dim3(1), dim3(kFsThreads), 0, s, (const double*)F->d_by, (const double*)vec(kVw),
+                      (const double*)vec(kVdw), (const double*)vec(kVv), (const double*)vec(kVgv),
+                      (const double*)F->d_Binv, (const double*)vec(kVpart), Rp, nw, mu, vec(kVwu), vec(kVscal));
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   NFFT4GP_HIP_CHECK(hipMemcpyAsync(F->sc, vec(kVscal), sizeof(double) * 5, hipMemcpyDeviceToHost, s));
+   NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+   F->logabsdet = lad - (double)(Rp - F->R) * std::log(mu);  // the padded slots' pivots are mu
+   F->det_sign = sign;
+   F->fl = l;
+   F->fmu = mu;
+   F->factored = true;
+   return 0;
+}
+
+int grow_counts(FeatureGp* F, size_t nblk)
+{
+   if (nblk <= F->cnt_cap) return 0;
+   if (F->d_cnt) (void)hipFree(F->d_cnt);
+   F->d_cnt = nullptr;
+   F->cnt_cap = 0;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_cnt, sizeof(unsigned int) * nblk));
+   F->cnt_cap = nblk;
+   return 0;
+}
+
+// out = a y + c Z coef at the n rows of X (X, y, out: host or device); *n_outside: the rows outside the domain
+int fgp_apply(FeatureGp* F, const double* coef, const double* X, int n, long long ldim, const double* y, double a,
+              double c, double* out, long long* n_outside)
+{
+   hipStream_t s = current_stream();
+   double *xown = nullptr, *yown = nullptr, *oown = nullptr;
+   auto body = [&]() -> int {
+      const double *dX, *dy = nullptr;
+      long long ld, ldy;
+      if (stage(X, (size_t)n, (size_t)F->d, (size_t)ldim, s, &dX, &ld, &xown)) return -1;
+      if (y && stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &yown)) return -1;
+      double* dout = out;
+      const bool odev = is_device_ptr(out);
+      if (!odev) {
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&oown, sizeof(double) * (size_t)n));
+         dout = oown;
+      }
+      const int per = kFaThreads * kFaPts;
+      const size_t nblk = ((size_t)n + per - 1) / per;
+      if (grow_counts(F, nblk)) return -1;
+      hipLaunchKernelGGL(k_fgp_apply, dim3((unsigned int)nblk), dim3(kFaThreads), sizeof(double) * (size_t)F->Rp, s, coef,
+                         F->Rp, (const double*)F->d_centre, (const double*)F->d_scale, (const int*)F->d_feature, F->nw,
+                         dX, ld, n, dy, a, c, dout, F->d_cnt);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (!odev) NFFT4GP_HIP_CHECK(hipMemcpyAsync(out, oown, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+      std::vector<unsigned int> h(nblk);
+      NFFT4GP_HIP_CHECK(hipMemcpyAsync(h.data(), F->d_cnt, sizeof(unsigned int) * nblk, hipMemcpyDeviceToHost, s));
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      long long t = 0;
+      for (unsigned int v : h) t += v;
+      *n_outside = t;
+      return 0;
+   };
+   const int rc = body();
+   (void)hipStreamSynchronize(s);  // nothing in flight reads the staging buffers
+   for (double* p : {xown, yown, oown})
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
+}  // namespace
+}  // namespace nfft4gp_amd
+
+using namespace nfft4gp_amd;
+
+extern "C" {
+
+void* Nfft4GPAmdFeatureGpCreate(void* additive_handle, const double* X, int n, int ldim, int d, const double* y)
+{
+   const char* who = "nfft4gp_amd: Nfft4GPAmdFeatureGpCreate";
+   if (!device_ok()) {
+      fprintf(stderr, "%s: no HIP device visible.\n", who);
+      return NULL;
+   }
+   AdditivePlan* Pp = additive_plan_of(additive_handle);
+   if (!Pp || !X || !y) {
+      fprintf(stderr, "%s needs an additive handle of this library (a distributed operator has none), X and y.\n", who);
+      return NULL;
+   }
+   AdditivePlan& P = *Pp;
+   const char* why = nullptr;
+   if (!P.points_ready || !P.d_w)
+      why = "no Gaussian / Matern-1/2 setup call has been made on the handle";
+   else if (P.row_begin != 0 || P.row_end != P.n_global)
+      why = "the handle is a row shard";
+   else if (P.diag != 1.0 || P.weight != 1.0 / (double)P.nw)
+      why = "the handle is a component shard";
+   else if (P.md.on || (int)P.comp_feature.size() != P.nw || (int)P.comp_centre.size() != P.nw)
+      why = "every window must have exactly one feature";
+   else if (n != P.n || n < 1)
+      why = "n is not the handle's number of points";
+   else if (d != P.d || ldim < n)
+      why = "d is not the handle's number of columns, or ldim < n";
+   else if (P.nw > kMvMaxNw)
+      why = "more than 128 windows (an R x R matrix would exceed 170 MB)";
+   if (!why)
+      for (int c = 0; c < P.nw; c++)
+         if (P.comp_dims[c] != 1 || P.comp_feature[c] < 0 || P.comp_feature[c] >= P.d)
+            why = "every window must have exactly one feature";
+   if (why) {
+      fprintf(stderr, "%s: %s.\n", who, why);
+      return NULL;
+   }
+   FeatureGp* F = new FeatureGp();
+   F->n = n;
+   F->nw = P.nw;
+   F->d = P.d;
+   F->kernel = P.kernel;
+   F->Rp = mv_order(P.nw);
+   F->R = kMvFeat * P.nw;
+   F->scale = P.comp_scale;
+   hipStream_t s = current_stream();
+   double *xown = nullptr, *yown = nullptr;
+   const int Rp = F->Rp;
+   auto body = [&]() -> int {
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_centre, sizeof(double) * P.nw));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_scale, sizeof(double) * P.nw));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_feature, sizeof(int) * P.nw));
+      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_centre, P.comp_centre.data(), sizeof(double) * P.nw, hipMemcpyHostToDevice));
+      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_scale, P.comp_scale.data(), sizeof(double) * P.nw, hipMemcpyHostToDevice));
+      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_feature, P.comp_feature.data(), sizeof(int) * P.nw, hipMemcpyHostToDevice));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_G, sizeof(double) * (size_t)Rp * Rp));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_by, sizeof(double) * ((size_t)Rp + 1)));
+      const double *dX, *dy;
+      long long ld, ldy;
+      if (stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &dX, &ld, &xown) ||
+          stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &yown))
+         return -1;
+      const WindowMap W = window_map(F);
+      long long outside = 0;
+      if (window_count_outside(W, dX, ld, n, s, &outside)) return -1;
+      if (outside) {
+         fprintf(stderr, "%s: %lld of %d rows of X lie outside the handle's domain: X is not the handle's data.\n", who,
+                 outside, n);
+         return -1;
+      }
+      if (window_moments(W, dX, ld, n, dy, F->d_G, F->d_by, F->d_by + Rp, nullptr, s)) return -1;
+      NFFT4GP_HIP_CHECK(hipMemcpy(&F->yy, F->d_by + Rp, sizeof(double), hipMemcpyDeviceToHost));
+      return 0;
+   };
+   const int rc = body();
+   (void)hipStreamSynchronize(s);
+   for (double* p : {xown, yown})
+      if (p) (void)hipFree(p);
+   if (rc) {
+      fgp_free(F);
+      return NULL;
+   }
+   return F;
+}
+
+int Nfft4GPAmdFeatureGpSetOptions(void* fgp, nfft4gp_transform_type transform, const int* mask)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || (int)transform < 0 || (int)transform > 3) return -1;
+   F->transform = (int)transform;
+   F->has_mask = mask != nullptr;
+   for (int i = 0; i < 3; i++) F->mask[i] = mask ? mask[i] : 1;
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpLoss(void* fgp, double* x, double* lossp, double* dloss)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || !x || !lossp || !dloss) return -1;
+   double t[3], dt[3];
+   for (int i = 0; i < 3; i++)
+      if (Nfft4GPTransform((nfft4gp_transform_type)F->transform, x[i], 0, t + i, dt + i)) return -1;
+   const double f = t[0], l = t[1], mu = t[2];
+   if (!(mu > 0.0) || !std::isfinite(f) || f == 0.0) return -1;
+   if (fgp_factor(F, l, mu)) return -1;
+   const double n = (double)F->n, R = (double)F->R, ff = f * f;
+   const double bv = F->sc[0], vGv = F->sc[1], uwu = F->sc[2], trBinv = F->sc[3], trBdG = F->sc[4];
+   const double q = (F->yy - bv) / mu;                             // y^T M^{-1} y
+   const double my2 = (F->yy - 2.0 * bv + vGv) / (mu * mu);        // |M^{-1} y|^2
+   const double logdet = n * std::log(ff) + (n - R) * std::log(mu) + F->logabsdet;
+   const double loss = 0.5 * (q / (ff * n) + logdet / n + std::log(2.0 * 3.1415926535897932384626));
+   const double L1[3] = {2.0 * q / (ff * f) / n, uwu / ff / n, my2 / ff / n};
+   const double L2[3] = {2.0 / f, trBdG / n, ((n - R) / mu + trBinv) / n};
+   double g[3];
+   bool finite = std::isfinite(loss);
+   for (int i = 0; i < 3; i++) {
+      g[i] = 0.5 * (-L1[i] + L2[i]) * dt[i];
+      finite = finite && std::isfinite(g[i]);
+      if (F->has_mask && !F->mask[i]) g[i] = 0.0;
+   }
+   if (!finite) return -1;
+   *lossp = loss;
+   for (int i = 0; i < 3; i++) dloss[i] = g[i];
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpSolve(void* fgp, const double* X, int n, int ldim, int d, const double* y, double f, double l,
+                             double mu, double* alpha)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || !X || !y || !alpha || n != F->n || d != F->d || ldim < n || !std::isfinite(f) || f == 0.0) return -1;
+   if (fgp_factor(F, l, mu)) return -1;
+   const double a = 1.0 / (f * f * mu);
+   long long outside = 0;
+   if (fgp_apply(F, F->d_vec + (size_t)kVv * F->Rp, X, n, (long long)ldim, y, a, -a, alpha, &outside)) return -1;
+   if (outside) {
+      fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdFeatureGpSolve: %lld of %d rows of X lie outside the domain: X is not the "
+                      "data the object was created over.\n", outside, n);
+      return -2;
+   }
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpSolveRhs(void* fgp, const double* X, int n, int ldim, int d, const double* r, double f, double l,
+                                double mu, double* alpha)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || !X || !r || !alpha || n != F->n || d != F->d || ldim < n || !std::isfinite(f) || f == 0.0) return -1;
+   if (fgp_factor(F, l, mu)) return -1;
+   hipStream_t s = current_stream();
+   const int Rp = F->Rp;
+   double *xown = nullptr, *rown = nullptr, *tmp = nullptr;  // tmp: Z^T r, r^T r, then v in place of w o Z^T r
+   long long outside = 0;
+   auto body = [&]() -> int {
+      const double *dX, *dr;
+      long long ld, ldr;
+      if (stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &dX, &ld, &xown) ||
+          stage(r, (size_t)n, 1, (size_t)n, s, &dr, &ldr, &rown))
+         return -1;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&tmp, sizeof(double) * (2 * (size_t)Rp + 1)));
+      if (window_moments(window_map(F), dX, ld, n, dr, nullptr, tmp, tmp + Rp, nullptr, s)) return -1;
+      double* v = tmp + Rp + 1;
+      hipLaunchKernelGGL(k_fgp_hadamard, dim3((Rp + 255) / 256), dim3(256), 0, s, (const double*)F->d_vec,
+                         (const double*)tmp, Rp, v);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (lu_resolve_dev(F->d_B, Rp, F->d_piv, v, 1, s)) return -1;
+      const double a = 1.0 / (f * f * mu);
+      return fgp_apply(F, v, dX, n, ld, dr, a, -a, alpha, &outside);
+   };
+   int rc = body();
+   (void)hipStreamSynchronize(s);
+   for (double* p : {xown, rown, tmp})
+      if (p) (void)hipFree(p);
+   if (!rc && outside) {
+      fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdFeatureGpSolveRhs: %lld of %d rows of X lie outside the domain.\n", outside,
+              n);
+      rc = -2;
+   }
+   return rc;
+}
+
+int Nfft4GPAmdFeatureGpVariance(void* fgp, double f, double l, double mu, double* S)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   (void)f;  // S does not depend on f: the model applies f^2
+   if (!F || !S) return -1;
+   if (fgp_factor(F, l, mu)) return -1;
+   hipStream_t s = current_stream();
+   const int R = F->R;
+   const bool sdev = is_device_ptr(S);
+   double* dS = S;
+   if (!sdev) NFFT4GP_HIP_CHECK(hipMalloc((void**)&dS, sizeof(double) * (size_t)R * R));
+   hipLaunchKernelGGL(k_fgp_variance, dim3((R + 255) / 256, R), dim3(256), 0, s, (const double*)F->d_Binv,
+                      (const double*)F->d_vec, F->Rp, R, mu, dS);
+   int rc = hipGetLastError() == hipSuccess ? 0 : -1;
+   if (!sdev) {
+      if (!rc && hipMemcpyAsync(S, dS, sizeof(double) * (size_t)R * R, hipMemcpyDeviceToHost, s) != hipSuccess) rc = -1;
+      if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+      (void)hipFree(dS);
+   }
+   return rc;
+}
+
+int Nfft4GPAmdFeatureGpPredict(void* fgp, double f, double l, double mu, const double* Xnew, int n_new, int ldim, int d,
+                               double* mean, long long* n_outside)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   (void)f;  // phi^T (w o u) = K(x*, X) A^{-1} y: f^2 cancels
+   if (!F || d != F->d || n_new < 0 || ldim < n_new) return -1;
+   if (n_outside) *n_outside = 0;
+   if (n_new == 0) return 0;
+   if (!Xnew || !mean) return -1;
+   if (fgp_factor(F, l, mu)) return -1;
+   long long outside = 0;
+   if (fgp_apply(F, F->d_vec + (size_t)kVwu * F->Rp, Xnew, n_new, (long long)ldim, nullptr, 0.0, 1.0, mean, &outside))
+      return -1;
+   if (n_outside) *n_outside = outside;
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpMoments(void* fgp, double* G, double* b, double* yy)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F) return -1;
+   const int Rp = F->Rp, R = F->R;
+   auto slot = [](int i) { return i / kMvFeat * kMvPad + i % kMvFeat; };
+   if (G) {
+      std::vector<double> h((size_t)Rp * Rp);
+      NFFT4GP_HIP_CHECK(hipMemcpy(h.data(), F->d_G, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+      for (int i = 0; i < R; i++)
+         for (int j = 0; j < R; j++) G[(size_t)i * R + j] = h[(size_t)slot(i) * Rp + slot(j)];
+   }
+   if (b) {
+      std::vector<double> h((size_t)Rp);
+      NFFT4GP_HIP_CHECK(hipMemcpy(h.data(), F->d_by, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+      for (int i = 0; i < R; i++) b[i] = h[slot(i)];
+   }
+   if (yy) *yy = F->yy;
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpInfo(void* fgp, int* n, int* nw, int* R, int* kernel)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F) return -1;
+   if (n) *n = F->n;
+   if (nw) *nw = F->nw;
+   if (R) *R = F->R;
+   if (kernel) *kernel = F->kernel;
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpStatus(void* fgp, int* det_sign, double* logabsdet)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F) return -1;
+   if (det_sign) *det_sign = F->det_sign;
+   if (logabsdet) *logabsdet = F->logabsdet;
+   return 0;
+}
+
+void Nfft4GPAmdFeatureGpFree(void* fgp) { fgp_free((FeatureGp*)fgp); }
+
+int Nfft4GPAmdModelFeatureWeightsGrad(int kernel, double l, double scale, int nw, double* dw33)
+{
+   if ((kernel != 0 && kernel != 1) || !(l > 0.0) || !(scale > 0.0) || nw < 1 || !dw33) return -1;
+   feature_weights_grad(kernel, l, scale, nw, dw33);
+   return 0;
+}
+
+}  // extern "C"

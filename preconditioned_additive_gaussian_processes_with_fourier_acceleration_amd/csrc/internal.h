@@ -350,8 +350,15 @@ int sym_eig_host(const std::vector<double>& A, int n, std::vector<double>& w, st
 int chol_inverse_host(std::vector<double>& A, int k);
 // B <- A^{-1} B, A n x n general, B n x nrhs, column-major: LU with partial pivoting on the host, and on device
 // arrays (ld n) by rocSOLVER getrf / getrs with the host LU as the fallback; 0, zero pivot column + 1, or -1
-int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs);
-int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s);
+// logabsdet / sign (may be NULL): log |det A| summed over U's diagonal in a fixed order and the determinant's sign
+// from that diagonal and the row interchanges.  piv_keep (device, n ints; may be NULL): the row interchanges are
+// left there and A holds the factors on either route, so that lu_resolve_dev can solve further right-hand sides.
+int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs, double* logabsdet = nullptr,
+                  int* sign = nullptr, std::vector<int>* piv_out = nullptr);
+void lu_subst_host(const std::vector<double>& A, int n, const std::vector<int>& piv, std::vector<double>& B, int nrhs);
+int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s, double* logabsdet = nullptr,
+                 int* sign = nullptr, int* piv_keep = nullptr);
+int lu_resolve_dev(const double* A, int n, const int* piv, double* B, int nrhs, hipStream_t s);
 struct Comm;
 // a row shard of the Nystrom setup: this process holds rows [row_begin, row_begin + n) of n_global; the
 // Gram is all-reduced over comm and rank 0's k x k factors are broadcast (dist.hip)
@@ -460,6 +467,52 @@ void* afn_create_device(int n, int k, int* d_perm, double* d_Linv, double* d_Lin
 hipStream_t current_stream();
 bool is_device_ptr(const void* p);
 int device_ok();
+
+// ---- the operator's finite-rank form with 1-D windows (model.hip, feature_gp.hip) ------------
+// A = f^2 (Z W Z^T + mu I): per window 33 features [cos 2 pi k xs, k = 0..16 | sin 2 pi k xs, k = 1..16] of the
+// window's quantised coordinate; a window takes kMvPad slots and the windows are padded to a multiple of 4.
+constexpr int kMvFeat = 33, kMvPad = 36, kMvMaxNw = 128;  // an R_p x R_p matrix at 128 windows: 170 MB
+constexpr double kMpLimit = 0.25 + 1.0 / 8589934592.0;    // the domain: |xs| <= 1/4 + 2^-33
+inline int mv_order(int nw) { return kMvPad * ((nw + 3) / 4 * 4); }  // R_p
+
+// cos and sin of 2 pi xs_q, xs_q the window's quantised coordinate (quantize(): what k_model_predict decodes its
+// cell and offset from); false when the point is outside the window's domain (the angle is then 0)
+__device__ inline bool mv_angle(double x, double ctr, double sc, double& c1, double& s1)
+{
+   const double xs = (x - ctr) * sc;
+   const bool in = fabs(xs) <= kMpLimit;
+   const double xq = in ? xs : 0.0;
+   const uint32_t q = (uint32_t)(unsigned long long)llround(xq * 4294967296.0);
+   sincospi((double)(int)q * (1.0 / 2147483648.0), &s1, &c1);  // |xs| <= 1/4: (int)q 2^-32 is xs_q
+   return in;
+}
+
+// (cos, sin) k theta -> (k + 1) theta: a rotation, whose error grows linearly in k (<= 16 steps)
+__device__ inline void mv_rotate(double& ck, double& sk, double c1, double s1)
+{
+   const double c = ck * c1 - sk * s1;
+   sk = sk * c1 + ck * s1;
+   ck = c;
+}
+
+// the windows of a handle or a model: device arrays of nw entries
+struct WindowMap {
+   int nw = 0, d = 0;
+   const double* centre = nullptr;
+   const double* scale = nullptr;
+   const int* feature = nullptr;
+};
+// the 33 weights of one window (W's diagonal) and their derivative in l
+void feature_weights(int kernel, double l, double scale, int nw, double* w33);
+void feature_weights_grad(int kernel, double l, double scale, int nw, double* dw33);
+// the number of rows of dX (n x d device, ld) with a coordinate outside some window's domain
+int window_count_outside(const WindowMap& W, const double* dX, long long ld, int n, hipStream_t s, long long* outside);
+// G = Z^T Z (R_p x R_p device, column-major) over the n rows of dX, Z formed in chunks whose Grams are added in
+// chunk order; with dy (n, device) also b = Z^T y (R_p) and yy = y^T y (yy == b + R_p) by a feature-generating
+// reduction with per-workgroup partials summed in block order (G may then be NULL: only b and yy).  ms2 (may be NULL):
+// wall clock of the features and of the Grams.  Deterministic: no atomics, every sum in a fixed order.
+int window_moments(const WindowMap& W, const double* dX, long long ld, int n, const double* dy, double* G, double* b,
+                   double* yy, double* ms2, hipStream_t s);
 
 // ---- libc rand() of the reference (nfft_api.cpp) --------------------------------------------------
 // The reference draws libc rand() (Nfft4GPRandPerm, Nfft4GPVecRand, rankest.c), so after the same srand()

@@ -35,7 +35,6 @@ constexpr int kMpThreads = 256;
 constexpr int kMpPts = 4;                  // points per thread (strided by the workgroup: coalesced columns)
 constexpr int kMpGroup = 8;                // windows staged in LDS per pass (8 x 513 doubles = 32.8 KB)
 constexpr int kMpWin = kNC * kNos + 1;     // [window][degree][cell], windows 513 doubles apart (k_interp_hl)
-constexpr double kMpLimit = 0.25 + 1.0 / 8589934592.0;  // 1/4 + 2^-33
 
 struct Model {
    int nw = 0, d = 0, kernel = 0;
@@ -246,28 +245,7 @@ int model_predict(Model* M, const double* Xnew, int n_new, long long ldim, doubl
 // steps) and the windows are padded to a multiple of 4 (k_model_std's column tile), R_p = 36 * 4 ceil(nw / 4); the
 // added slots have zero features and zero weight, so mu I + W G keeps mu on their diagonal and S is zero there.
 typedef double d4 __attribute__((ext_vector_type(4)));
-constexpr int kMvFeat = 33, kMvPad = 36, kMvMaxNw = 128;  // S at 128 windows: 4608^2 doubles = 170 MB
-inline int mv_order(int nw) { return kMvPad * ((nw + 3) / 4 * 4); }  // R_p
-
-// cos and sin of 2 pi xs_q, xs_q the window's quantised coordinate (quantize(): what k_model_predict decodes its
-// cell and offset from); false when the point is outside the window's domain (the angle is then 0)
-__device__ inline bool mv_angle(double x, double ctr, double sc, double& c1, double& s1)
-{
-   const double xs = (x - ctr) * sc;
-   const bool in = fabs(xs) <= kMpLimit;
-   const double xq = in ? xs : 0.0;
-   const uint32_t q = (uint32_t)(unsigned long long)llround(xq * 4294967296.0);
-   sincospi((double)(int)q * (1.0 / 2147483648.0), &s1, &c1);  // |xs| <= 1/4: (int)q 2^-32 is xs_q
-   return in;
-}
-
-// (cos, sin) k theta -> (k + 1) theta: a rotation, whose error grows linearly in k (<= 16 steps)
-__device__ inline void mv_rotate(double& ck, double& sk, double c1, double s1)
-{
-   const double c = ck * c1 - sk * s1;
-   sk = sk * c1 + ck * s1;
-   ck = c;
-}
+// (the slot constants, mv_order, mv_angle and mv_rotate are internal.h's: feature_gp.hip shares them)
 
 // per workgroup the number of rows with a coordinate outside some window's domain
 __global__ __launch_bounds__(256) void k_model_outside(const double* __restrict__ centre,
@@ -322,6 +300,91 @@ __global__ __launch_bounds__(256) void k_model_features(const double* __restrict
    for (int j = kMvFeat; j < kMvPad; j++) z[j * ldz] = 0.0;
 }
 
+// Z^T y and y^T y without Z: part[block][slot] = the block's sum of feature(slot) y over its points, slot R_p the
+// block's sum of y^2.  A thread owns kZyPts points (strided by the workgroup) and regenerates their features window
+// by window as k_model_features does (the same bits); each of a window's 33 sums folds over the wave in a fixed
+// butterfly, then over the 4 waves in wave order.  k_model_sum_parts adds the blocks in block order: no atomics, the
+// same bits every time.
+constexpr int kZyThreads = 256, kZyPts = 4;
+
+__device__ inline double zy_wave_sum(double v)
+{
+#pragma unroll
+   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+   return v;
+}
+
+__global__ __launch_bounds__(kZyThreads) void k_model_zty(const double* __restrict__ centre,
+                                                          const double* __restrict__ scale,
+                                                          const int* __restrict__ feature, int nw,
+                                                          const double* __restrict__ X, long long ldim, int n,
+                                                          const double* __restrict__ y, int Rp,
+                                                          double* __restrict__ part)
+{
+   __shared__ double s_w[kZyThreads / kWave][kMvPad];
+   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+   const long long base = (long long)blockIdx.x * (kZyThreads * kZyPts) + tid;
+   double* out = part + (size_t)blockIdx.x * (Rp + 1);
+   double yv[kZyPts];
+   double yy = 0.0;
+#pragma unroll
+   for (int p = 0; p < kZyPts; p++) {
+      const long long i = base + (long long)p * kZyThreads;
+      yv[p] = (i < n) ? y[i] : 0.0;  // a point past the end adds exact zeros
+      yy = fma(yv[p], yv[p], yy);
+   }
+   yy = zy_wave_sum(yy);
+   if (lane == 0) s_w[wave][0] = yy;
+   __syncthreads();
+   if (tid == 0) out[Rp] = ((s_w[0][0] + s_w[1][0]) + s_w[2][0]) + s_w[3][0];
+   for (int c = 0; c < Rp / kMvPad; c++) {
+      __syncthreads();  // the previous window's sums have been read
+      if (c >= nw) {    // a padded window (uniform over the workgroup)
+         if (tid < kMvPad) out[c * kMvPad + tid] = 0.0;
+         continue;
+      }
+      const double ctr = centre[c], sc = scale[c];
+      const double* col = X + (size_t)feature[c] * (size_t)ldim;
+      double c1[kZyPts], s1[kZyPts], ck[kZyPts], sk[kZyPts];
+#pragma unroll
+      for (int p = 0; p < kZyPts; p++) {
+         const long long i = base + (long long)p * kZyThreads;
+         (void)mv_angle((i < n) ? col[i] : ctr, ctr, sc, c1[p], s1[p]);
+         ck[p] = 1.0;
+         sk[p] = 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k <= 16; k++) {
+         double vc = 0.0, vs = 0.0;
+#pragma unroll
+         for (int p = 0; p < kZyPts; p++) {
+            vc = fma(yv[p], ck[p], vc);
+            vs = fma(yv[p], sk[p], vs);
+            mv_rotate(ck[p], sk[p], c1[p], s1[p]);
+         }
+         vc = zy_wave_sum(vc);
+         if (lane == 0) s_w[wave][k] = vc;
+         if (k) {
+            vs = zy_wave_sum(vs);
+            if (lane == 0) s_w[wave][16 + k] = vs;
+         }
+      }
+      __syncthreads();
+      if (tid < kMvPad)
+         out[c * kMvPad + tid] = tid < kMvFeat ? ((s_w[0][tid] + s_w[1][tid]) + s_w[2][tid]) + s_w[3][tid] : 0.0;
+   }
+}
+
+// out[slot] = sum over the blocks of part[block][slot], in block order
+__global__ void k_model_sum_parts(const double* __restrict__ part, int nblk, int count, double* __restrict__ out)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= count) return;
+   double v = 0.0;
+   for (int b = 0; b < nblk; b++) v += part[(size_t)b * count + i];
+   out[i] = v;
+}
+
 __global__ void k_model_add(double* __restrict__ G, const double* __restrict__ Gc, long long count)
 {
    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -345,17 +408,125 @@ __global__ void k_model_symmetrise(const double* __restrict__ B, int Rp, double*
    if (i < Rp) S[i + (size_t)j * Rp] = 0.5 * (B[i + (size_t)j * Rp] + B[j + (size_t)i * Rp]);
 }
 
-// the 33 weights of one window: w[cos 0] = b^_0 / nw, w[cos k] = w[sin k] = 2 b^_k / nw (k = 1..15),
-// w[cos 16] = w[sin 16] = b^_{-16} / nw (the band's one unpaired mode), b^ indexed k + 16
+// points per chunk of Z: the chunk stays <= 256 MB
+int chunk_points(int n, int Rp)
+{
+   const long long cap = std::max<long long>(1024, (32LL << 20) / Rp / 16 * 16);
+   return (int)std::min<long long>(n, cap);
+}
+
+// b^ (index k + 16) -> the 33 weights: [cos 0] = b^_0 / nw, [cos k] = [sin k] = 2 b^_k / nw (k = 1..15),
+// [cos 16] = [sin 16] = b^_{-16} / nw (the band's one unpaired mode)
+void weight_map(const double* bh, double mult, int nw, double* w33)
+{
+   w33[0] = mult * bh[16] / nw;
+   for (int k = 1; k <= 15; k++) w33[k] = w33[16 + k] = mult * (2.0 * bh[16 + k]) / nw;
+   w33[16] = w33[32] = mult * bh[0] / nw;
+}
+
+}  // namespace
+
+// the 33 weights of one window, from the kernel's b^ at plan_setup's comp_sigma
 void feature_weights(int kernel, double l, double scale, int nw, double* w33)
 {
    double bh[kBand];
-   const double sig = (kernel == 0) ? l * scale * std::sqrt(2.0) : l * scale;  // plan_setup's comp_sigma
+   const double sig = (kernel == 0) ? l * scale * std::sqrt(2.0) : l * scale;
    bhat_1d(kernel == 0 ? 0 : 2, sig, bh);
-   w33[0] = bh[16] / nw;
-   for (int k = 1; k <= 15; k++) w33[k] = w33[16 + k] = 2.0 * bh[16 + k] / nw;
-   w33[16] = w33[32] = bh[0] / nw;
+   weight_map(bh, 1.0, nw, w33);
 }
+
+// dW / dl: the same map of the derivative kernel's b^ times plan_setup's dscale (what the gradient matvec applies)
+void feature_weights_grad(int kernel, double l, double scale, int nw, double* dw33)
+{
+   double bh[kBand];
+   const double sig = (kernel == 0) ? l * scale * std::sqrt(2.0) : l * scale;
+   bhat_1d(kernel == 0 ? 1 : 3, sig, bh);
+   const double dscale = (kernel == 0) ? 2.0 * scale * std::sqrt(2.0) / sig : scale / sig;
+   weight_map(bh, dscale, nw, dw33);
+}
+
+int window_count_outside(const WindowMap& W, const double* dX, long long ld, int n, hipStream_t s, long long* outside)
+{
+   const size_t nblk = ((size_t)n + 255) / 256;
+   unsigned int* d_cnt = nullptr;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)&d_cnt, sizeof(unsigned int) * std::max<size_t>(1, nblk)));
+   std::vector<unsigned int> h(nblk);
+   hipLaunchKernelGGL(k_model_outside, dim3((unsigned int)nblk), dim3(256), 0, s, W.centre, W.scale, W.feature, W.nw,
+                      dX, ld, n, d_cnt);
+   const bool ok = hipGetLastError() == hipSuccess &&
+                   hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned int) * nblk, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                   hipStreamSynchronize(s) == hipSuccess;
+   (void)hipFree(d_cnt);
+   if (!ok) return -1;
+   long long t = 0;
+   for (unsigned int v : h) t += v;
+   *outside = t;
+   return 0;
+}
+
+// Z in chunks -> their Grams (gram_tn: split sum in a fixed order) added in chunk order; Z^T y and y^T y by
+// k_model_zty (b and yy must be contiguous: b + R_p == yy)
+int window_moments(const WindowMap& W, const double* dX, long long ld, int n, const double* dy, double* G, double* b,
+                   double* yy, double* ms2, hipStream_t s)
+{
+   const int Rp = mv_order(W.nw);
+   const size_t rr = (size_t)Rp * Rp;
+   double *Z = nullptr, *Gc = nullptr, *part = nullptr;
+   auto body = [&]() -> int {
+      if (dy) {
+         if (yy != b + Rp) return -1;
+         const int per = kZyThreads * kZyPts;
+         const int nblk = (int)(((long long)n + per - 1) / per);
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&part, sizeof(double) * (size_t)nblk * (Rp + 1)));
+         hipLaunchKernelGGL(k_model_zty, dim3(nblk), dim3(kZyThreads), 0, s, W.centre, W.scale, W.feature, W.nw, dX, ld,
+                            n, dy, Rp, part);
+         hipLaunchKernelGGL(k_model_sum_parts, dim3((Rp + 1 + 255) / 256), dim3(256), 0, s, (const double*)part, nblk,
+                            Rp + 1, b);
+         NFFT4GP_HIP_CHECK(hipGetLastError());
+         if (!G) {
+            NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+            return 0;
+         }
+      }
+      const int chunk = chunk_points(n, Rp);
+      const long long ldz = ((long long)chunk + 15) / 16 * 16;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Z, sizeof(double) * (size_t)ldz * Rp));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Gc, sizeof(double) * rr));
+      NFFT4GP_HIP_CHECK(hipMemsetAsync(G, 0, sizeof(double) * rr, s));
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      double ms[2] = {0.0, 0.0};
+      auto t0 = std::chrono::steady_clock::now();
+      auto lap = [&](int which) {  // the stream is idle: gram_tn synchronises
+         const auto t1 = std::chrono::steady_clock::now();
+         ms[which] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+         t0 = t1;
+      };
+      for (long long i0 = 0; i0 < n; i0 += chunk) {
+         const int cnt = (int)std::min<long long>(chunk, n - i0);
+         hipLaunchKernelGGL(k_model_features, dim3((cnt + 255) / 256, Rp / kMvPad), dim3(256), 0, s, W.centre, W.scale,
+                            W.feature, W.nw, dX, ld, i0, cnt, Z, ldz);
+         NFFT4GP_HIP_CHECK(hipGetLastError());
+         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+         lap(0);
+         if (gram_tn(Rp, Rp, cnt, Z, ldz, Z, ldz, Gc, 1, s)) return -1;
+         lap(1);
+         hipLaunchKernelGGL(k_model_add, dim3((unsigned int)((rr + 255) / 256)), dim3(256), 0, s, G,
+                            (const double*)Gc, (long long)rr);
+         NFFT4GP_HIP_CHECK(hipGetLastError());
+      }
+      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      lap(1);
+      if (ms2) ms2[0] = ms[0], ms2[1] = ms[1];
+      return 0;
+   };
+   const int rc = body();
+   (void)hipStreamSynchronize(s);
+   for (double* p : {Z, Gc, part})
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
+namespace {
 
 // X (n x d, ld ldim; host or device) as a device array: *dX, *ld; *owned is to be freed by the caller
 int stage_points(const Model* M, const double* X, int n, long long ldim, hipStream_t s, const double** dX,
@@ -395,72 +566,34 @@ int read_counts(Model* M, size_t nblk, hipStream_t s, long long* total)
    return 0;
 }
 
-// points per chunk of Z: the chunk stays <= 256 MB
-int chunk_points(int n, int Rp)
-{
-   const long long cap = std::max<long long>(1024, (32LL << 20) / Rp / 16 * 16);
-   return (int)std::min<long long>(n, cap);
-}
-
-// The fit: Z in chunks -> their Grams (gram_tn: split sum in a fixed order) added in chunk order -> mu I + W G
-// -> LU -> S.  Every step is deterministic, so two fits give the same bits.  Returns 0, -1, or -2 (rows outside).
+// The fit: G = Z^T Z (window_moments) -> mu I + W G -> LU -> S.  Every step is deterministic, so two fits give the
+// same bits.  Returns 0, -1, or -2 (rows outside).
 int model_fit_variance(Model* M, const double* X, int n, long long ldim)
 {
    hipStream_t s = current_stream();
    const int nw = M->nw, Rp = mv_order(nw);
    const size_t rr = (size_t)Rp * Rp;
-   double *xown = nullptr, *Z = nullptr, *G = nullptr, *Gc = nullptr, *A = nullptr, *S = nullptr, *d_w = nullptr;
+   double *xown = nullptr, *G = nullptr, *Gc = nullptr, *A = nullptr, *S = nullptr, *d_w = nullptr;
    auto body = [&]() -> int {
       const double* dX;
       long long ld;
       if (stage_points(M, X, n, ldim, s, &dX, &ld, &xown)) return -1;
-      const size_t nblk = ((size_t)n + 255) / 256;
+      const WindowMap W{nw, M->d, M->d_centre, M->d_scale, M->d_feature};
       long long outside = 0;
-      if (grow_counts(M, nblk)) return -1;
-      hipLaunchKernelGGL(k_model_outside, dim3((unsigned int)nblk), dim3(256), 0, s, (const double*)M->d_centre,
-                         (const double*)M->d_scale, (const int*)M->d_feature, nw, dX, ld, n, M->d_cnt);
-      NFFT4GP_HIP_CHECK(hipGetLastError());
-      if (read_counts(M, nblk, s, &outside)) return -1;
+      if (window_count_outside(W, dX, ld, n, s, &outside)) return -1;
       if (outside) {
          fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdModelFitVariance: %lld of %d rows lie outside the model's domain; "
                          "the model is unchanged.\n", outside, n);
          return -2;
       }
-      const int chunk = chunk_points(n, Rp);
-      const long long ldz = ((long long)chunk + 15) / 16 * 16;
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Z, sizeof(double) * (size_t)ldz * Rp));
       NFFT4GP_HIP_CHECK(hipMalloc((void**)&G, sizeof(double) * rr));
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Gc, sizeof(double) * rr));
-      NFFT4GP_HIP_CHECK(hipMemsetAsync(G, 0, sizeof(double) * rr, s));
-      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
       double ms[3] = {0.0, 0.0, 0.0};
-      auto t0 = std::chrono::steady_clock::now();
-      auto lap = [&](int which) {  // the stream is idle: gram_tn and lu_solve_dev synchronise
-         const auto t1 = std::chrono::steady_clock::now();
-         ms[which] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-         t0 = t1;
-      };
-      for (long long i0 = 0; i0 < n; i0 += chunk) {
-         const int cnt = (int)std::min<long long>(chunk, n - i0);
-         hipLaunchKernelGGL(k_model_features, dim3((cnt + 255) / 256, Rp / kMvPad), dim3(256), 0, s,
-                            (const double*)M->d_centre, (const double*)M->d_scale, (const int*)M->d_feature, nw, dX,
-                            ld, i0, cnt, Z, ldz);
-         NFFT4GP_HIP_CHECK(hipGetLastError());
-         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
-         lap(0);
-         if (gram_tn(Rp, Rp, cnt, Z, ldz, Z, ldz, Gc, 1, s)) return -1;
-         lap(1);
-         hipLaunchKernelGGL(k_model_add, dim3((unsigned int)((rr + 255) / 256)), dim3(256), 0, s, G,
-                            (const double*)Gc, (long long)rr);
-         NFFT4GP_HIP_CHECK(hipGetLastError());
-      }
-      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
-      lap(1);
-      (void)hipFree(Z);
-      Z = nullptr;
+      if (window_moments(W, dX, ld, n, nullptr, G, nullptr, nullptr, ms, s)) return -1;
+      const auto t0 = std::chrono::steady_clock::now();
       std::vector<double> w((size_t)Rp, 0.0);
       for (int c = 0; c < nw; c++) feature_weights(M->kernel, M->l, M->scale[c], nw, w.data() + (size_t)c * kMvPad);
       if (to_device(&d_w, w.data(), w.size())) return -1;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&Gc, sizeof(double) * rr));
       NFFT4GP_HIP_CHECK(hipMalloc((void**)&A, sizeof(double) * rr));
       NFFT4GP_HIP_CHECK(hipMalloc((void**)&S, sizeof(double) * rr));
       const dim3 g2((Rp + 255) / 256, Rp);
@@ -474,7 +607,7 @@ int model_fit_variance(Model* M, const double* X, int n, long long ldim)
       hipLaunchKernelGGL(k_model_symmetrise, g2, dim3(256), 0, s, (const double*)Gc, Rp, S);
       NFFT4GP_HIP_CHECK(hipGetLastError());
       NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
-      lap(2);
+      ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       for (int i = 0; i < 3; i++) M->fit_ms[i] = ms[i];
       std::swap(M->d_S, S);  // the previous matrix, if any, is freed below
       M->R = kMvFeat * nw;
@@ -482,7 +615,7 @@ int model_fit_variance(Model* M, const double* X, int n, long long ldim)
    };
    const int rc = body();
    (void)hipStreamSynchronize(s);
-   for (double* p : {xown, Z, G, Gc, A, S, d_w})
+   for (double* p : {xown, G, Gc, A, S, d_w})
       if (p) (void)hipFree(p);
    return rc;
 }

@@ -679,8 +679,10 @@ int sym_eigvals_dev(double* A, int n, std::vector<double>& w, hipStream_t s)
 }
 
 // B <- A^{-1} B by LU with partial pivoting (dgetrf / dgetrs semantics; A n x n and B n x nrhs column-major, A
-// overwritten by its factors); returns 0 or the first zero pivot's column + 1
-int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs)
+// overwritten by its factors); returns 0 or the first zero pivot's column + 1.  logabsdet / sign (may be NULL):
+// log |det A| = sum_j log |u_jj| in the order j = 0 .. n - 1, and the sign of det A from the u_jj and the interchanges
+int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrhs, double* logabsdet, int* sign,
+                  std::vector<int>* piv_out)
 {
    std::vector<int> piv(n);
    for (int j = 0; j < n; j++) {
@@ -701,6 +703,25 @@ int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrh
             for (int i = j + 1; i < n; i++) cc[i] -= cj[i] * u;
       }
    }
+   if (logabsdet || sign) {
+      double lad = 0.0;
+      int sg = 1;
+      for (int j = 0; j < n; j++) {
+         const double u = A[j + (size_t)j * n];
+         lad += std::log(std::fabs(u));
+         if ((u < 0.0) != (piv[j] != j)) sg = -sg;
+      }
+      if (logabsdet) *logabsdet = lad;
+      if (sign) *sign = sg;
+   }
+   lu_subst_host(A, n, piv, B, nrhs);
+   if (piv_out) piv_out->swap(piv);
+   return 0;
+}
+
+// B <- A^{-1} B from lu_solve_host's factors and interchanges (piv[j]: the row exchanged with row j, 0-based)
+void lu_subst_host(const std::vector<double>& A, int n, const std::vector<int>& piv, std::vector<double>& B, int nrhs)
+{
    for (int c = 0; c < nrhs; c++) {
       double* b = B.data() + (size_t)c * n;
       for (int j = 0; j < n; j++) std::swap(b[j], b[piv[j]]);  // whole rows were interchanged: P first, then L
@@ -715,7 +736,6 @@ int lu_solve_host(std::vector<double>& A, int n, std::vector<double>& B, int nrh
             for (int i = 0; i < j; i++) b[i] -= A[i + (size_t)j * n] * v;
       }
    }
-   return 0;
 }
 
 // L^{-1} of chol(A) (lower) in place; returns 0 or the failing column + 1
@@ -768,35 +788,116 @@ int chol_inverse_dev(double* A, int k, double shift, double* G, double* Gt, int*
 // X = A^{-1} B in place of B: A n x n general (overwritten by its LU), B n x nrhs, both column-major with leading
 // dimension n on the device.  rocSOLVER getrf / getrs when they loaded, otherwise a host LU with partial pivoting
 // (row interchanges, columns eliminated left to right: the same answer to rounding).  Returns 0, the first zero
-// pivot's column + 1 when A is singular, or -1.
-int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s)
+// pivot's column + 1 when A is singular, or -1.  logabsdet / sign (may be NULL): from the factor's diagonal and
+// the pivots (k_lu_logdet), on either route; A keeps the factor on the rocSOLVER route.
+constexpr int kLdThreads = 256;
+
+// out[0] = sum_j log |u_jj|, out[1] = the determinant's sign: thread t adds the columns t, t + 256, .. in order,
+// then the 256 partial sums fold in a fixed tree (ipiv: getrf's 1-based row interchanges)
+__global__ __launch_bounds__(kLdThreads) void k_lu_logdet(const double* __restrict__ A, int n,
+                                                          const int* __restrict__ ipiv, double* __restrict__ out)
+{
+   __shared__ double s_sum[kLdThreads];
+   __shared__ int s_neg[kLdThreads];
+   const int t = threadIdx.x;
+   double acc = 0.0;
+   int neg = 0;
+   for (int j = t; j < n; j += kLdThreads) {
+      const double u = A[j + (size_t)j * n];
+      acc += log(fabs(u));
+      neg ^= (int)((u < 0.0) != (ipiv[j] != j + 1));
+   }
+   s_sum[t] = acc;
+   s_neg[t] = neg;
+   __syncthreads();
+   for (int h = kLdThreads / 2; h > 0; h >>= 1) {
+      if (t < h) {
+         s_sum[t] += s_sum[t + h];
+         s_neg[t] ^= s_neg[t + h];
+      }
+      __syncthreads();
+   }
+   if (t == 0) {
+      out[0] = s_sum[0];
+      out[1] = s_neg[0] ? -1.0 : 1.0;
+   }
+}
+
+int lu_solve_dev(double* A, int n, double* B, int nrhs, hipStream_t s, double* logabsdet, int* sign, int* piv_keep)
 {
    RocSolver& R = rocsolver();
    if (R.ok && R.getrf && R.getrs) {
-      int *d_piv = nullptr, *d_info = nullptr;
+      int *d_piv = piv_keep, *d_info = nullptr;
       int info = 0, rc = -1;
-      if (dalloc(&d_piv, n) == 0 && dalloc(&d_info, 1) == 0) {
+      if ((d_piv || dalloc(&d_piv, n) == 0) && dalloc(&d_info, 1) == 0) {
          R.set_stream(R.h, s);
          if (R.getrf(R.h, n, n, A, n, d_piv, d_info) == rocblas_status_success &&
              hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipStreamSynchronize(s) == hipSuccess) {
+            bool ok = true;
+            if (!info && (logabsdet || sign)) {
+               double* d_out = nullptr;
+               double h[2] = {0.0, 1.0};
+               ok = dalloc(&d_out, 2) == 0;
+               if (ok) {
+                  hipLaunchKernelGGL(k_lu_logdet, dim3(1), dim3(kLdThreads), 0, s, (const double*)A, n,
+                                     (const int*)d_piv, d_out);
+                  ok = hipGetLastError() == hipSuccess &&
+                       hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess &&
+                       hipStreamSynchronize(s) == hipSuccess;
+               }
+               (void)hipFree(d_out);
+               if (logabsdet) *logabsdet = h[0];
+               if (sign) *sign = h[1] < 0.0 ? -1 : 1;
+            }
             if (info)
                rc = info;
-            else if (R.getrs(R.h, rocblas_operation_none, n, nrhs, A, n, d_piv, B, n) == rocblas_status_success &&
+            else if (ok && R.getrs(R.h, rocblas_operation_none, n, nrhs, A, n, d_piv, B, n) == rocblas_status_success &&
                      hipStreamSynchronize(s) == hipSuccess)
                rc = 0;
          }
       }
-      (void)hipFree(d_piv);
+      if (!piv_keep) (void)hipFree(d_piv);
       (void)hipFree(d_info);
       return rc;
    }
    std::vector<double> a((size_t)n * n), b((size_t)n * nrhs);
+   std::vector<int> piv;
    if (hipMemcpyAsync(a.data(), A, sizeof(double) * a.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
        hipMemcpyAsync(b.data(), B, sizeof(double) * b.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
        hipStreamSynchronize(s) != hipSuccess)
       return -1;
-   if (int info = lu_solve_host(a, n, b, nrhs)) return info;
+   if (int info = lu_solve_host(a, n, b, nrhs, logabsdet, sign, &piv)) return info;
+   if (piv_keep) {  // the factors and getrf's 1-based interchanges, for lu_resolve_dev
+      for (int& p : piv) p += 1;
+      if (hipMemcpy(A, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(piv_keep, piv.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess)
+         return -1;
+   }
+   return hipMemcpy(B, b.data(), sizeof(double) * b.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+// B <- A^{-1} B from the factors and pivots a lu_solve_dev call with piv_keep left behind (same route as that call)
+int lu_resolve_dev(const double* A, int n, const int* piv, double* B, int nrhs, hipStream_t s)
+{
+   RocSolver& R = rocsolver();
+   if (R.ok && R.getrf && R.getrs) {
+      R.set_stream(R.h, s);
+      return R.getrs(R.h, rocblas_operation_none, n, nrhs, const_cast<double*>(A), n, piv, B, n) ==
+                         rocblas_status_success &&
+                     hipStreamSynchronize(s) == hipSuccess
+                 ? 0
+                 : -1;
+   }
+   std::vector<double> a((size_t)n * n), b((size_t)n * nrhs);
+   std::vector<int> p(n);
+   if (hipMemcpyAsync(a.data(), A, sizeof(double) * a.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipMemcpyAsync(b.data(), B, sizeof(double) * b.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipMemcpyAsync(p.data(), piv, sizeof(int) * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipStreamSynchronize(s) != hipSuccess)
+      return -1;
+   for (int& v : p) v -= 1;
+   lu_subst_host(a, n, p, b, nrhs);
    return hipMemcpy(B, b.data(), sizeof(double) * b.size(), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
 
@@ -1148,6 +1249,13 @@ extern "C" int Nfft4GPAmdHostLuSolve(const double* A, int n, double* B, int nrhs
    if (info) return info;
    memcpy(B, b.data(), sizeof(double) * b.size());
    return 0;
+}
+
+extern "C" int Nfft4GPAmdHostLuLogdet(const double* A, int n, double* logabsdet, int* sign)
+{
+   if (!A || n < 1 || !logabsdet || !sign) return -1;
+   std::vector<double> a(A, A + (size_t)n * n), b;
+   return nfft4gp_amd::lu_solve_host(a, n, b, 0, logabsdet, sign);
 }
 
 // ---- device test hooks (tests/ only): the MFMA GEMM and the panel kernel in isolation ---------------

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .feature_gp import FeatureGP
 from .model import FittedModel
 from .nfft import GAUSSIAN, NFFTAdditiveKernel
 
@@ -117,7 +118,7 @@ def gp_predict(X, Xp, windows, nwindows, dwindows, y, hyper, maxits=100, tol=1e-
 
 
 def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, tol=1e-3,
-           op=None, **loss_kwargs):
+           op=None, exact=False, **loss_kwargs):
     """Adam on the GP loss, run by the library: Nfft4GPGpProblemSetup carries gp_loss's arguments,
     Nfft4GPOptimizationAdamStep calls Nfft4GPGpProblemLoss and updates the hyperparameters (``hyper0`` = (f, l, mu)
     before the transform), for at most ``steps`` steps or until the gradient norm falls below ``tol``.
@@ -125,7 +126,11 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
     Returns (hyper_history [nits + 1, 3], loss_history [nits], grad_norm_history [nits], flag): entry k of the
     loss and gradient-norm histories belongs to hyper_history[k]; flag is the last step's status (1 steps
     reached, 2 gradient norm below tol, -1 the loss failed).  The library prints one line per step, as the
-    reference does."""
+    reference does.
+    ``exact=True`` (1-D windows): the same Adam entry points step on Nfft4GPAmdFeatureGpLoss instead -- the loss and
+    gradient of the operator's finite-rank form, exact and deterministic, with no solve and no probes (of
+    ``loss_kwargs`` only transform and mask apply); the kernel is the one ``op`` was last set up with, Gaussian for
+    a new op."""
     unknown = set(loss_kwargs) - {"maxits", "nvecs", "rademacher", "transform", "mask", "print_level", "loss_tol"}
     if unknown:
         raise TypeError(f"unknown loss arguments: {sorted(unknown)}")
@@ -163,6 +168,8 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
         r_ptr = R.ctypes.data
     m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
     L = _lib.lib()
+    if exact:
+        return _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, m)
     adam = L.Nfft4GPOptimizationAdamCreate()
     prob = L.Nfft4GPGPProblemCreate()
     try:
@@ -183,11 +190,7 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
         flag = 0
         while flag == 0:
             flag = L.Nfft4GPOptimizationAdamStep(adam)
-        st = _lib.OptimizerAdamStruct.from_address(adam)
-        nits = st._nits
-        hyper = np.ctypeslib.as_array(st._x_history, shape=(nits + 1, 3)).copy()
-        loss = np.ctypeslib.as_array(st._loss_history, shape=(steps + 1,))[:nits].copy()
-        gnorm = np.ctypeslib.as_array(st._grad_norm_history, shape=(steps + 1,))[:nits].copy()
+        hyper, loss, gnorm = _adam_histories(adam, steps)
     finally:
         L.Nfft4GPOptimizationAdamFree(adam)
         L.Nfft4GPGPProblemFree(prob)
@@ -195,11 +198,53 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
     return hyper, loss, gnorm, int(flag)
 
 
-def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None, variance=False):
+def _adam_histories(adam, steps):
+    st = _lib.OptimizerAdamStruct.from_address(adam)
+    nits = st._nits
+    hyper = np.ctypeslib.as_array(st._x_history, shape=(nits + 1, 3)).copy()
+    loss = np.ctypeslib.as_array(st._loss_history, shape=(steps + 1,))[:nits].copy()
+    gnorm = np.ctypeslib.as_array(st._grad_norm_history, shape=(steps + 1,))[:nits].copy()
+    return hyper, loss, gnorm
+
+
+def _set_up_once(op, x0, transform):
+    """a FeatureGP needs a handle whose points are fixed: one setup call at the starting hyperparameters when ``op``
+    has had none (the centres and scales do not depend on them)"""
+    if op._kernel is None:
+        f, l, mu = FeatureGP.transformed(x0, transform)
+        if op.setup(GAUSSIAN, f=f, l=l, mu=mu) != 0:
+            raise RuntimeError("the kernel setup failed")
+
+
+def _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, mask):
+    _set_up_once(op, x0, transform)
+    fgp = FeatureGP(op, X, lab)
+    adam = L.Nfft4GPOptimizationAdamCreate()
+    try:
+        if L.Nfft4GPAmdFeatureGpSetOptions(fgp.h, int(transform), mask.ctypes.data if mask is not None else None) or \
+                L.Nfft4GPOptimizationAdamSetProblem(adam, _lib.fnptr("Nfft4GPAmdFeatureGpLoss"), fgp.h, 3) or \
+                L.Nfft4GPOptimizationAdamSetOptions(adam, steps, float(tol), float(beta1), float(beta2), float(eps),
+                                                    float(lr)) or \
+                L.Nfft4GPOptimizationAdamInit(adam, x0.ctypes.data):
+            raise RuntimeError("the optimiser setup failed")
+        flag = 0
+        while flag == 0:
+            flag = L.Nfft4GPOptimizationAdamStep(adam)
+        hyper, loss, gnorm = _adam_histories(adam, steps)
+    finally:
+        L.Nfft4GPOptimizationAdamFree(adam)
+        fgp.free()
+    return hyper, loss, gnorm, int(flag)
+
+
+def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None, variance=False,
+             exact=False):
     """The fitted model at the hyperparameters ``hyper`` = (f, l, mu) before the transform: sets the kernel up
     (Gaussian, or the kernel ``op`` was last set up with), solves f^2 (K + mu I) alpha = y with FGMRES on the
     device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse.
-    ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works."""
+    ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works.
+    ``exact=True`` (1-D windows): FeatureGP.model instead -- alpha from the feature-space solve and the variance
+    matrix from the same factorisation, no FGMRES (tol, maxits and variance do not apply: S is always loaded)."""
     import torch
 
     from .solvers import fgmres
@@ -213,6 +258,13 @@ def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, tra
         kernel = op._kernel
     if op.n != X.shape[0] or len(y) != op.n:
         raise ValueError("X, y and op must have the same number of points")
+    if exact:
+        _set_up_once(op, hyper, transform)
+        fgp = FeatureGP(op, X, y)
+        try:
+            return fgp.model(X, y, hyper, transform=transform)
+        finally:
+            fgp.free()
     L = _lib.lib()
     t, dt = C.c_double(), C.c_double()
     flm = []

@@ -521,7 +521,14 @@ const char *Nfft4GPAmdVersion(void);
  * NFFT4GP_AMD_* variables): [10]=spread variant (0-3), [11]=1 if the spread adds its grids with global
  * atomics (0: partial grids, summed by the grid kernel), [12]=threads per interpolation workgroup (512 or
  * 1024), [13]=1 if a plain matvec (no gradient, no fused dot) takes the LDS-staged interpolation
- * (k_interp_hl), [14]=that kernel's staging slots, [15]=threads per two-vector interpolation workgroup.
+ * (k_interp_hl), [14]=that kernel's staging slots, [15]=threads per two-vector interpolation workgroup,
+ * [16]=1 if a plain matvec and the solvers' fused matvec-dot run in two launches (fused_grid): every
+ * interpolation workgroup applies the circulants to the spread's summed grids and builds the polynomials of the
+ * 33 cells that hold points in its own LDS, with no grid kernel.  That needs [11], one GPU, 1-D windows, no
+ * deterministic mode, [12] = 1024 and [13] = 0, at most 256 blocks, and an LDS need of
+ * 8 (block + 32) + 8 nwindows (265 + 45 + 65 + 65) + 264 bytes within 160 KB; NFFT4GP_AMD_FUSED_GRID=0 / 1, read when
+ * the handle is created, forces it off / lifts the block bound (1 still refuses where the path cannot run).  A
+ * matvec captured into a HIP graph keeps the three launches.
  * Only the first nout entries are written. */
 int Nfft4GPAmdAdditiveLayoutInfo(void *str, long long *out, int nout);
 

@@ -239,6 +239,12 @@ struct AdditivePlan {
    double* d_part2 = nullptr; // two-vector matvec: both vectors' partial grids [2][nblocks][nw][64]
    double* d_gsum = nullptr;  // the spread's grids summed by global atomics [nw][64] (launch_spread_grid), zero between
                               // matvecs (k_grid clears what it read)
+   // the fused matvec (launch_matvec_fused): -1 the layout decides (pick_fused_grid), 0 / 1 NFFT4GP_AMD_FUSED_GRID
+   int fused_grid = -1;
+   bool cells33 = false;      // every quantised coordinate lies in the 33 cells 48..63, 0..16 (plan_build_points)
+   double* d_hsum = nullptr;  // [2][nw][64] the fused matvec's grid sums (the spread's global atomics, as d_gsum); the
+                              // one of parity hsum_par is zero between fused matvecs
+   int hsum_par = 0;
    double* d_H2 = nullptr;    // [2][nw][64][kNC]
    double* d_xs = nullptr;    // staging (host pointer calls)
    double* d_ys = nullptr;    // staging 3n
@@ -307,6 +313,12 @@ int pick_interp_threads(const AdditivePlan& P);   // launch_interp's workgroup: 
 bool pick_interp_hl(const AdditivePlan& P);       // a plain matvec (no gradient, no fused dot) takes k_interp_hl
 int pick_hl_slots(const AdditivePlan& P);         // k_interp_hl's staging slots ns
 int pick_interp2_threads();                       // k_interp2's workgroup: 512 or 1024
+bool pick_fused_grid(const AdditivePlan& P);      // a plain matvec (and the fused dot) runs launch_matvec_fused
+// The plain matvec in two launches, for handles with pick_fused_grid(P): the spread adds its grids into a sum buffer
+// (as launch_spread_grid's), and every interpolation workgroup applies the circulants and builds the polynomials of
+// the 33 cells that hold points in its own LDS from those sums.  No k_grid launch; P.d_H is not written.
+int launch_matvec_fused(AdditivePlan& P, double alpha, const double* d_x, double beta, double* d_y, hipStream_t stream,
+                        double* d_dot = nullptr);
 // y_v = beta y_v + alpha A x_v for nv device vectors of this library's additive handle (pairs per layout pass)
 int additive_matvec_multi(void* str, int nv, double alpha, const double* const* X, double beta, double* const* Y);
 // y = A x (alpha = 1, beta = 0) and *d_dot = (y, x) on device pointers: the matvec + dot of a CG step in

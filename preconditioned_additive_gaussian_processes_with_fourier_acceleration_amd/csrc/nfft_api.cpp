@@ -111,6 +111,7 @@ namespace {
 
 struct TimingRec {
    std::array<hipEvent_t, 6> ev;  // start / stop of the spread, grid and interp dispatches
+   bool grid = true;              // false: the matvec had no grid dispatch (launch_matvec_fused), ev[2], ev[3] unrecorded
 };
 
 struct PlanExt {
@@ -168,6 +169,7 @@ void free_plan(PlanExt* E)
    dfree(P.d_Hd);
    dfree(P.d_hb);
    dfree(P.d_gsum);
+   dfree(P.d_hsum);
    dfree(P.d_C);
    dfree(P.d_xs);
    dfree(P.d_ys);
@@ -256,13 +258,22 @@ int plan_build_points(AdditivePlan& P, const double* buffer)
    // windows are independent: one host thread per window at a time (centre, scale, quantize)
    const auto t0 = std::chrono::steady_clock::now();
    std::atomic<int> next{0};
+   // |xs| <= 1/4 after centre_and_scale, so a point's cell q >> 26 is one of 48..63, 0..16: (q + 2^30) >> 26 <= 32.
+   // The fused matvec keeps those 33 cells' polynomials only (pick_fused_grid); checked here, while q is at hand.
+   std::atomic<int> outside33{0};
    auto work = [&]() {
       std::vector<double> xw;
       for (int c = next++; c < P.nw; c = next++) {
          const double* col = buffer + (size_t)c * ng * P.dw;  // nfft_interface.c:703 stride n*dwindows
          P.comp_scale[c] = centre_and_scale(col, ng, 1, xw, &P.comp_centre[c]);
          if (P.comp_scale[c] < 0.0) continue;
-         for (int j = 0; j < P.n; j++) qc[(size_t)c * P.n + j] = quantize(xw[(size_t)P.row_begin + j]);
+         uint32_t cimax = 0;
+         for (int j = 0; j < P.n; j++) {
+            const uint32_t q = quantize(xw[(size_t)P.row_begin + j]);
+            qc[(size_t)c * P.n + j] = q;
+            cimax = std::max(cimax, (q + 0x40000000u) >> 26);
+         }
+         if (cimax > 32u) outside33 = 1;
       }
    };
    {
@@ -279,6 +290,7 @@ int plan_build_points(AdditivePlan& P, const double* buffer)
                  "0.25/radius (nfft_interface.c:190) is undefined there.\n", c);
          return -1;
       }
+   P.cells33 = outside33 == 0;
    const auto t1 = std::chrono::steady_clock::now();
    // the layout is built on the GPU from the quantised coordinates (layout_gpu.hip); layout.cpp builds the
    // same arrays on the host when a (block, group) would not fit the GPU builder's LDS (B > 4064, or CG > 4
@@ -374,6 +386,20 @@ TimingRec get_rec(PlanExt* E)
    return r;
 }
 
+// The fused two-launch matvec serves this call: the handle qualifies (pick_fused_grid) and the stream is not being
+// captured -- the sum buffers' parity flips on the host per matvec, so a replayed graph would add into a buffer that
+// nothing has cleared; a captured matvec keeps the three launches, whose k_grid clears what it read
+bool use_fused(const AdditivePlan& P, hipStream_t s)
+{
+   if (!pick_fused_grid(P)) return false;
+   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+   if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+   }
+   return st == hipStreamCaptureStatusNone;
+}
+
 // y = beta*y + alpha*(op) x  on device pointers
 int plan_apply_dev(PlanExt* E, int grad, double alpha, const double* d_x, double beta, double* d_y)
 {
@@ -387,6 +413,8 @@ int plan_apply_dev(PlanExt* E, int grad, double alpha, const double* d_x, double
    const bool mdt = P.timing && P.md.on;  // multi-feature windows: events recorded around each launch
    int rc = 0;
    if (mdt) (void)hipEventRecord(rec.ev[0], s);
+   const bool fused = !grad && use_fused(P, s);
+   rec.grid = !fused;
    if (P.md.on) {
       rc = md_spread(P, d_x, P.md.d_grid, s);
       if (mdt) {
@@ -394,6 +422,8 @@ int plan_apply_dev(PlanExt* E, int grad, double alpha, const double* d_x, double
          (void)hipEventRecord(rec.ev[2], s);
       }
       if (!rc) rc = md_grid(P, P.md.d_grid, grad, s);
+   } else if (fused) {
+      rc = launch_matvec_fused(P, alpha, d_x, beta, d_y, s);
    } else {
       rc = launch_spread_grid(P, d_x, grad, s);
    }
@@ -401,7 +431,7 @@ int plan_apply_dev(PlanExt* E, int grad, double alpha, const double* d_x, double
       (void)hipEventRecord(rec.ev[3], s);
       (void)hipEventRecord(rec.ev[4], s);
    }
-   if (!rc)
+   if (!rc && !fused)
       rc = P.md.on ? md_interp(P, grad, alpha, d_x, beta, d_y, s) : launch_interp(P, grad, alpha, d_x, beta, d_y, s);
    if (mdt) (void)hipEventRecord(rec.ev[5], s);
    P.kev = nullptr;
@@ -549,6 +579,7 @@ void env_layout(AdditivePlan& P)
    if (const char* e = getenv("NFFT4GP_AMD_SPREAD_FOLD")) P.spread_fold = atoi(e) != 0;
    if (const char* e = getenv("NFFT4GP_AMD_DET")) P.det = atoi(e) != 0;
    if (const char* e = getenv("NFFT4GP_AMD_PRECISION")) P.rec = atoi(e) == 32 ? 4 : 5;
+   if (const char* e = getenv("NFFT4GP_AMD_FUSED_GRID")) P.fused_grid = atoi(e) != 0;
 }
 
 void* additive_create(double* data, int n_global, int ldim, int d, int* windows, int nwindows, int dwindows, int rb,
@@ -621,6 +652,7 @@ int additive_matvec_dot(void* str, const double* d_x, double* d_y, double* d_dot
       if (md_spread(P, d_x, P.md.d_grid, s) || md_grid(P, P.md.d_grid, 0, s)) return -1;
       return md_interp(P, 0, 1.0, d_x, 0.0, d_y, s, d_dot);
    }
+   if (use_fused(P, s)) return launch_matvec_fused(P, 1.0, d_x, 0.0, d_y, s, d_dot);
    if (launch_spread_grid(P, d_x, 0, s)) return -1;
    return launch_interp(P, 0, 1.0, d_x, 0.0, d_y, s, d_dot);
 }
@@ -914,11 +946,11 @@ int Nfft4GPAmdAdditiveLayoutInfo(void* str, long long* out, int nout)
    PlanExt* E = additive_plan(str);
    if (!E || !out) return -1;
    const AdditivePlan& P = E->P;
-   // [10 .. 15]: the launchers' own decisions (internal.h pick_*), for the handle as it stands now
-   long long v[16] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
+   // [10 .. 16]: the launchers' own decisions (internal.h pick_*), for the handle as it stands now
+   long long v[17] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
                       (long long)P.dl.bytes, pick_spread_variant(P), grid_atomic(P), pick_interp_threads(P),
-                      pick_interp_hl(P), pick_hl_slots(P), pick_interp2_threads()};
-   for (int i = 0; i < nout && i < 16; i++) out[i] = v[i];
+                      pick_interp_hl(P), pick_hl_slots(P), pick_interp2_threads(), pick_fused_grid(P)};
+   for (int i = 0; i < nout && i < 17; i++) out[i] = v[i];
    return 0;
 }
 
@@ -976,6 +1008,7 @@ int Nfft4GPAmdTimingQuery(void* str, double* ms, long long* cnt)
    for (auto& r : E->pending) {
       NFFT4GP_HIP_CHECK(hipEventSynchronize(r.ev[5]));
       for (int i = 0; i < 3; i++) {
+         if (i == 1 && !r.grid) continue;  // a fused matvec: no grid dispatch to count
          float t = 0.f;
          NFFT4GP_HIP_CHECK(hipEventElapsedTime(&t, r.ev[2 * i], r.ev[2 * i + 1]));
          P.ms[i] += t;
@@ -1131,7 +1164,8 @@ int Nfft4GPAmdShardFinish(void* str, const double* grid, int grad, double alpha,
 }
 
 // debugging: the circulant coefficients H ([nw][64][kNC]) of the last grid pass into out (count doubles at
-// most); returns the number copied, or -1
+// most); returns the number copied, or -1.  A fused matvec (pick_fused_grid) has no grid pass and leaves d_H alone:
+// after one this returns the H of the last three-launch pass (gradient, two-vector, shard), stale, not -1
 long long Nfft4GPAmdDebugShardH(void* str, double* out, long long count)
 {
    PlanExt* E = additive_plan(str);

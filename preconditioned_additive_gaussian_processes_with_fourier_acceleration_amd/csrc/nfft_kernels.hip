@@ -16,6 +16,8 @@
 //             Horner per point, ds_add_f64 into an LDS y-block; the epilogue applies
 //             y = beta*y + alpha*ff*(sum + mu*x) (grad: the three outputs of nfft_interface.c:547-549)
 //             in one coalesced pass.
+// The plain matvec of a handle with few blocks runs in two launches (launch_matvec_fused): k_interp_fg does k_grid's
+// work in every workgroup's prologue, for the 33 cells that hold points, and reads H from LDS.
 // Rejected experiments (persistent workgroups, prefetching runs, three-deep run rings, mixed-precision moments,
 // the grid step fused into the spread tail) are in the git history; DESIGN.md 3.5 has their numbers.
 #include <hip/hip_ext.h>
@@ -260,6 +262,15 @@ __device__ __forceinline__ double fold_window_mfma(const double (&a)[2], double*
    }
    return v;
 }
+
+// ---- the fused matvec (launch_matvec_fused): no k_grid launch ----
+// centre_and_scale leaves every 1-D coordinate in |x| <= 1/4, so a point's cell (q >> 26) is one of 48..63, 0..16:
+// kFgCells = 33 cells, compact index ci = (cell + 16) & 63.  Their taps reach the grid values cell - kM .. cell + kM + 1,
+// a span of kFgSpan = 42 from grid index kFgSpan0 = 44 (mod 64); every other grid value is an exact zero, and the
+// interpolation polynomials of the 33 cells read h = W g on the same span only.
+constexpr int kFgCells = 33;
+constexpr int kFgSpan = kFgCells + kTaps - 1;
+constexpr int kFgSpan0 = (kNos - 16 - kM) & (kNos - 1);
 
 // at most 80 VGPRs, so three 512-thread workgroups (24 waves) share a CU
 // PIPE (variant 3, layouts past the Infinity Cache): the next tile's loads issued before the current tile's moments
@@ -1090,6 +1101,185 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// the plain interpolation that builds its own H (the fused matvec, launch_matvec_fused)
+// ------------------------------------------------------------------------------------------------
+// gsum holds the windows' grids g, summed over the spread's workgroups by its global atomics (the spread is
+// launch_spread_grid's, unchanged); wcirc is d_w.  Every workgroup does k_grid's work for itself, on the 42 grid
+// values and 33 cells that matter (kFgSpan, kFgCells), in LDS:
+//   1. stage the nw x 64 sums and the nw x 64 circulant rows (windows 65 doubles apart: the windows of a wave on
+//      different banks) and clear s_y;
+//   2. h = W g on the span: h_c[k] = sum_j w[(k - j) & 63] g_c[j], compact indices k, j = 0..41 (grid index
+//      kFgSpan0 + k).  A thread forms four neighbouring outputs of one window: each step reads one g and one new w
+//      and feeds four FMAs (the other three w of the step were the previous steps' new ones), j ascending.  One
+//      output per thread would need two LDS reads per FMA: 1.5 us of LDS cycles per workgroup instead of 0.4;
+//   3. H[w][ci][d] = sum_tp h_c[ci + tp] C[tp][d] -- grid_tail's last step, the same FMAs in the same order --
+//      into [window][degree][ci], degrees kFgCells doubles apart and windows kFgWin = 8 x 33 + 1, so a wave's lanes,
+//      which walk runs of neighbouring cells, read neighbouring doubles (the 64-byte row per cell of d_H would put
+//      every fourth cell on the same banks).  A thread builds one (window, degree) over a quarter of the cells
+//      (9, 8, 8, 8): successive cells share 9 of their 10 h values, so 18 LDS reads feed up to 90 FMAs.
+// No workgroup waits for another: the sums were complete when the spread ended.  Block 0 also zeroes gclear, the sum
+// buffer the NEXT fused matvec's spread adds into (its last reader was the previous matvec's interpolation, which
+// stream order has finished).  The run loop and the epilogue are k_interp's plain path.
+constexpr int kFgWin = kNC * kFgCells + 1;
+constexpr int kFgRow = kNos + 1;          // a staged 64-entry row of g or w
+constexpr int kFgQuads = (kFgSpan + 3) / 4;  // 11 output quads cover the span
+constexpr int kFgHs = 4 * kFgQuads + 1;   // a window's h_c row (44 formed, 42 read)
+constexpr int kFgLdsWin = kFgWin + kFgHs + 2 * kFgRow;  // doubles of LDS per window
+
+template <int THREADS, bool DOT = false, int REC = 5>
+__global__ __launch_bounds__(THREADS) void k_interp_fg(
+    const uint16_t* __restrict__ meta, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ qarr,
+    const int* __restrict__ tile_off, const double* __restrict__ gsum, double* __restrict__ gclear,
+    const double* __restrict__ wcirc, const double* __restrict__ x, double* __restrict__ y, int n, int B, int ngroups,
+    double alpha, double beta, double f, double mu, double* __restrict__ dot_part,
+    unsigned int* __restrict__ dot_ticket, double* __restrict__ dot_out, int nw)
+{
+   static_assert(THREADS % (4 * kNC) == 0 && kNC == 8, "a thread keeps its degree and cell quarter over the build");
+   static_assert(kFgSpan % 6 == 0, "the circulant's steps go six per trip");
+   extern __shared__ __attribute__((aligned(16))) double smem[];
+   const int Bp = B + kPad;
+   double* s_y = smem;                         // the first dynamic slice (lds_add addresses it absolutely)
+   double* s_H = smem + Bp;                    // nw x kFgWin
+   double* s_h = s_H + (size_t)nw * kFgWin;    // nw x kFgHs: h on the span
+   double* s_g = s_h + (size_t)nw * kFgHs;     // nw x kFgRow: the summed grids
+   double* s_w = s_g + (size_t)nw * kFgRow;    // nw x kFgRow: the circulant rows
+   double* s_scr = s_w + (size_t)nw * kFgRow;  // DOT: kRedScratch bytes
+   const int b = blockIdx.x;
+   const int tid = threadIdx.x;
+   const int base = b * B;
+   const int nloc = min(B, n - base);
+   const int lane = tid & 63;
+   const int wave = tid >> 6;
+   constexpr int nwaves = THREADS / 64;
+   const int t0 = tile_off[b * ngroups];
+   const int t1 = tile_off[(b + 1) * ngroups];
+   TileRegs cur;
+   int t = t0 + wave;
+   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
+   // this thread's column of the tap table for step 3, fetched with the first tile (d = tid % 8 for every window)
+   double ct[kTaps];
+#pragma unroll
+   for (int tp = 0; tp < kTaps; tp++) ct[tp] = c_taps[tp * kNC + (tid & (kNC - 1))];
+   for (int i = tid; i < nw * kNos; i += THREADS) {
+      const int o = (i >> 6) * kFgRow + (i & (kNos - 1));
+      s_g[o] = gsum[i];
+      s_w[o] = wcirc[i];
+   }
+   if (b == 0)
+      for (int i = tid; i < nw * kNos; i += THREADS) gclear[i] = 0.0;
+   for (int i = tid; i < Bp; i += THREADS) s_y[i] = 0.0;
+   __syncthreads();
+   for (int it = tid; it < nw * kFgQuads; it += THREADS) {
+      const int w = it / kFgQuads, k0 = 4 * (it % kFgQuads);
+      const double* gw = s_g + w * kFgRow;
+      const double* ww = s_w + w * kFgRow;
+      double r3 = ww[(k0 + 3) & (kNos - 1)], r2 = ww[(k0 + 2) & (kNos - 1)], r1 = ww[(k0 + 1) & (kNos - 1)], r0 = ww[k0];
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 6
+      for (int j = 0; j < kFgSpan; j++) {
+         const double gj = gw[(kFgSpan0 + j) & (kNos - 1)];
+         a0 = fma(r0, gj, a0);
+         a1 = fma(r1, gj, a1);
+         a2 = fma(r2, gj, a2);
+         a3 = fma(r3, gj, a3);
+         r3 = r2, r2 = r1, r1 = r0;
+         r0 = ww[(k0 - j - 1) & (kNos - 1)];
+      }
+      double* hw = s_h + w * kFgHs + k0;
+      hw[0] = a0, hw[1] = a1, hw[2] = a2, hw[3] = a3;
+   }
+   __syncthreads();
+   {
+      const int d = tid & (kNC - 1), seg = (tid >> 3) & 3;
+      const int c0 = seg ? 8 * seg + 1 : 0, c1 = 8 * seg + 9;  // cells [c0, c1): 9, 8, 8, 8 of the 33
+      for (int w = tid >> 5; w < nw; w += THREADS / 32) {
+         const double* hw = s_h + w * kFgHs + c0;  // cell ci reads h_c[ci .. ci + 9]; c0 + 17 <= 42 < kFgHs
+         double hv[kTaps + 8];
+#pragma unroll
+         for (int j = 0; j < kTaps + 8; j++) hv[j] = hw[j];
+         double acc[9];
+#pragma unroll
+         for (int k = 0; k < 9; k++) acc[k] = 0.0;
+#pragma unroll
+         for (int tp = 0; tp < kTaps; tp++) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) acc[k] = fma(hv[k + tp], ct[tp], acc[k]);
+         }
+         double* dst = s_H + (size_t)w * kFgWin + d * kFgCells + c0;
+#pragma unroll
+         for (int k = 0; k < 9; k++)
+            if (c0 + k < c1) dst[k] = acc[k];
+      }
+   }
+   __syncthreads();
+   // the epilogue's x (mu term) and, when beta != 0, y are fetched now, behind the run loop: after the build, whose
+   // registers they would otherwise share, and after its barrier, which would wait for them
+   const bool ep_regs = B <= kEpMax * THREADS;
+   double xe[kEpMax], ye[kEpMax];
+   if (ep_regs) {
+#pragma unroll
+      for (int k = 0; k < kEpMax; k++) {
+         const int j = tid + k * THREADS;
+         xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
+         ye[k] = (beta != 0.0 && j < nloc) ? y[(size_t)base + j] : 0.0;
+      }
+   }
+
+   for (; t < t1; t += nwaves) {
+      const int tn = t + nwaves;
+      // meta is comp << 6 | cell; a cell outside the 33 cannot occur (pick_fused_grid), the min keeps the read in s_H
+      const int ci = min((int)((cur.mt + 16u) & 63u), kFgCells - 1);
+      const double* hrow = s_H + (size_t)(cur.mt >> 6) * kFgWin + ci;
+      double hc[kNC];
+#pragma unroll
+      for (int d = 0; d < kNC; d++) hc[d] = hrow[d * kFgCells];
+#pragma unroll
+      for (int r = 0; r < kR; r++) {
+         const uint32_t off = slot_off<REC>(cur, r);
+         const double u = q_to_s(cur.qq[r]);
+         double v = hc[kNC - 1];
+#pragma unroll
+         for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
+         lds_add(off, v);  // s_y is the first dynamic slice
+      }
+      if (tn < t1) load_tile<REC>(cur, meta, lo, qarr, tn, lane);
+   }
+   __syncthreads();
+
+   const double ff = f * f;
+   double dacc = 0.0;
+#pragma unroll
+   for (int k = 0; k < kEpMax; k++) {
+      if (!ep_regs) break;
+      const int j = tid + k * THREADS;
+      if (j >= nloc) break;
+      const double xj = xe[k];
+      const double v = ff * (s_y[j] + mu * xj);
+      const double yo = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
+      y[(size_t)base + j] = yo;
+      if (DOT) dacc = fma(yo, xj, dacc);
+   }
+   if (!ep_regs) {
+      for (int j = tid; j < nloc; j += THREADS) {
+         const size_t gj = (size_t)base + j;
+         const double xj = x[gj];
+         const double v = ff * (s_y[j] + mu * xj);
+         const double yo = (beta == 0.0) ? alpha * v : fma(beta, y[gj], alpha * v);
+         y[gj] = yo;
+         if (DOT) dacc = fma(yo, xj, dacc);
+      }
+   }
+   if (DOT) {
+      dacc = block_sum0_s<THREADS>(dacc, s_scr);
+      double tot;
+      if (grid_total_s<THREADS>(dacc, dot_part, dot_ticket, &tot, reinterpret_cast<int*>(s_scr + 2 * (THREADS / 64)),
+                                s_scr + THREADS / 64) &&
+          threadIdx.x == 0)
+         *dot_out = tot;
+   }
+}
+
+// ------------------------------------------------------------------------------------------------
 // two right-hand sides per pass over the layout (SLQ probes in lockstep, krylov.hip)
 // ------------------------------------------------------------------------------------------------
 // The interpolation reads the layout (5 B per (point, window)) once for both vectors and shares the
@@ -1293,6 +1483,16 @@ typedef void (*InterpPartFn)(const uint16_t*, const uint32_t*, const uint32_t*, 
                              int, int, int, double);
 static InterpPartFn interp_part_fn(int rec) { return rec == 4 ? k_interp_part<512, 4> : k_interp_part<512, 5>; }
 
+// the fused matvec's interpolation (launch_matvec_fused): 1024 threads, with or without the fused (q, p)
+typedef void (*InterpFgFn)(const uint16_t*, const uint32_t*, const uint32_t*, const int*, const double*, double*,
+                           const double*, const double*, double*, int, int, int, double, double, double, double,
+                           double*, unsigned int*, double*, int);
+static InterpFgFn interp_fg_fn(bool dot, int rec)
+{
+   if (rec == 4) return dot ? k_interp_fg<kInterpThreads, true, 4> : k_interp_fg<kInterpThreads, false, 4>;
+   return dot ? k_interp_fg<kInterpThreads, true, 5> : k_interp_fg<kInterpThreads, false, 5>;
+}
+
 // a kernel whose dynamic slice is addressed absolutely (lds_at) must have no static LDS
 static bool static_lds_zero(const void* fn)
 {
@@ -1362,6 +1562,17 @@ static std::vector<const void*> interp_kernels()
       for (int sm = 0; sm < 2; sm++)
          for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp2_fn(det, sm, rec));
    for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp_part_fn(rec));
+   for (int d = 0; d < 2; d++)
+      for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp_fg_fn(d, rec));
+   return v;
+}
+// every spread kernel the launchers pick
+static std::vector<const void*> spread_kernels()
+{
+   std::vector<const void*> v;
+   for (const auto& byrec : kSpreadFns)
+      for (const auto& bydet : byrec)
+         for (const SpreadFn f : bydet) v.push_back((const void*)f);
    return v;
 }
 
@@ -1369,10 +1580,8 @@ static void raise_lds_limit_once()
 {
    // a function-local static initialiser runs once (thread-safe)
    static const bool raised = []() {
-      for (const auto& byrec : kSpreadFns)
-         for (const auto& bydet : byrec)
-            for (const SpreadFn f : bydet)
-               (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
+      for (const void* f : spread_kernels())
+         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
       for (const void* f : interp_kernels())
          (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
       (void)hipGetLastError();
@@ -1386,9 +1595,7 @@ static bool abs_lds_ok()
 {
    static const bool ok = [] {
       std::vector<const void*> v = interp_kernels();
-      for (const auto& byrec : kSpreadFns)
-         for (const auto& bydet : byrec)
-            for (const SpreadFn f : bydet) v.push_back((const void*)f);
+      for (const void* f : spread_kernels()) v.push_back(f);
       for (const void* f : v)
          if (!static_lds_zero(f)) return false;
       return true;
@@ -1545,6 +1752,53 @@ int launch_interp(const AdditivePlan& P, int grad, double alpha, const double* d
              (const double*)P.d_Hd, d_x, d_y, P.n, P.B, P.ngroups, alpha, beta, P.f, P.mu * P.diag, P.diag,
              P.d_dot_part, P.d_dot_ticket, d_dot, (const double*)P.d_hb, P.nw);
    NFFT4GP_HIP_CHECK(hipGetLastError());
+   return 0;
+}
+
+// ---- the fused matvec: the spread's atomic grid sums + k_interp_fg, no k_grid launch and no d_H ----
+// k_interp_fg's LDS: the y slice, per window kFgLdsWin doubles (the 33 cells' polynomials, h on the span, the staged
+// grid sums and circulant row), and the fused dot's reduction scratch
+static size_t fg_lds_bytes(int B, int nw)
+{
+   return sizeof(double) * ((size_t)B + kPad) + sizeof(double) * (size_t)nw * kFgLdsWin + kRedScratch;
+}
+// Up to 256 blocks the 1024-thread interpolation runs one workgroup per CU whatever its LDS; past that two of
+// k_interp's workgroups share a CU and two of k_interp_fg's (145 KB at 32 windows) cannot, so the unfused path stays
+// (NFFT4GP_AMD_FUSED_GRID=1 runs the fused path there for an A/B)
+constexpr int kFusedMaxBlocks = 256;
+bool pick_fused_grid(const AdditivePlan& P)
+{
+   if (P.fused_grid == 0 || !P.cells33 || P.md.on || P.det || P.nblocks == 0 || P.n == 0) return false;
+   if (P.row_begin != 0 || P.row_end != P.n_global) return false;  // a row shard's grids are summed over the ranks
+   if (!grid_atomic(P) || pick_interp_threads(P) != kInterpThreads || pick_interp_hl(P)) return false;
+   if (fg_lds_bytes(P.B, P.nw) > kMaxDynamicLds) return false;
+   return P.fused_grid > 0 || P.nblocks <= kFusedMaxBlocks;
+}
+
+// y = beta y + alpha A x (d_dot: also (y, x), alpha = 1 and beta = 0) in two launches; the caller has checked
+// pick_fused_grid(P).  The two sum buffers P.d_hsum[0 / 1] are zero when allocated; this matvec's spread adds into
+// the one of the plan's parity, its interpolation reads that one and zeroes the other, and the parity flips.
+int launch_matvec_fused(AdditivePlan& P, double alpha, const double* d_x, double beta, double* d_y, hipStream_t stream,
+                        double* d_dot)
+{
+   raise_lds_limit_once();
+   if (!abs_lds_ok()) return -1;
+   if (d_dot && P.nblocks > kRedMaxBlocks) return -1;
+   const size_t ns = (size_t)P.nw * kNos;
+   if (!P.d_hsum) {
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&P.d_hsum, sizeof(double) * 2 * ns));
+      NFFT4GP_HIP_CHECK(hipMemsetAsync(P.d_hsum, 0, sizeof(double) * 2 * ns, stream));
+      P.hsum_par = 0;
+   }
+   double* S = P.d_hsum + (size_t)P.hsum_par * ns;
+   double* Sother = P.d_hsum + (size_t)(1 - P.hsum_par) * ns;
+   if (launch_spread_to(P, d_x, nullptr, S, stream)) return -1;
+   launch_ev(interp_fg_fn(d_dot != nullptr, P.rec), dim3(P.nblocks), dim3(kInterpThreads), fg_lds_bytes(P.B, P.nw),
+             stream, P.kev ? P.kev + 4 : nullptr, P.dl.meta, P.dl.lo, P.dl.q, P.dl.tile_off, (const double*)S, Sother,
+             (const double*)P.d_w, d_x, d_y, P.n, P.B, P.ngroups, alpha, beta, P.f, P.mu * P.diag, P.d_dot_part,
+             P.d_dot_ticket, d_dot, P.nw);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   P.hsum_par ^= 1;
    return 0;
 }
 

@@ -529,6 +529,7 @@ const char *Nfft4GPAmdVersion(void);
  * 8 (block + 32) + 8 nwindows (265 + 45 + 65 + 65) + 264 bytes within 160 KB; NFFT4GP_AMD_FUSED_GRID=0 / 1, read when
  * the handle is created, forces it off / lifts the block bound (1 still refuses where the path cannot run).  A
  * matvec captured into a HIP graph keeps the three launches.
+ * [17]=interpolation workgroups per block of a row shard's split finish (NFFT4GP_AMD_SHARD_SPLIT, read per call).
  * Only the first nout entries are written. */
 int Nfft4GPAmdAdditiveLayoutInfo(void *str, long long *out, int nout);
 

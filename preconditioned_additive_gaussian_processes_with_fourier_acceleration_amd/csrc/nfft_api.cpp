@@ -946,11 +946,11 @@ int Nfft4GPAmdAdditiveLayoutInfo(void* str, long long* out, int nout)
    PlanExt* E = additive_plan(str);
    if (!E || !out) return -1;
    const AdditivePlan& P = E->P;
-   // [10 .. 16]: the launchers' own decisions (internal.h pick_*), for the handle as it stands now
-   long long v[17] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
+   // [10 .. 17]: the launchers' own decisions (internal.h pick_*, shard_split), for the handle as it stands now
+   long long v[18] = {P.n, P.nw, P.B, P.nblocks, P.dl.ntiles, P.dl.ntiles * kWave * kR, kR, P.CG, P.ngroups,
                       (long long)P.dl.bytes, pick_spread_variant(P), grid_atomic(P), pick_interp_threads(P),
-                      pick_interp_hl(P), pick_hl_slots(P), pick_interp2_threads(), pick_fused_grid(P)};
-   for (int i = 0; i < nout && i < 17; i++) out[i] = v[i];
+                      pick_interp_hl(P), pick_hl_slots(P), pick_interp2_threads(), pick_fused_grid(P), shard_split(P)};
+   for (int i = 0; i < nout && i < 18; i++) out[i] = v[i];
    return 0;
 }
 

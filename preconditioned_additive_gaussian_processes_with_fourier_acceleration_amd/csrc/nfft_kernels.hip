@@ -16,6 +16,13 @@
 //             Horner per point, ds_add_f64 into an LDS y-block; the epilogue applies
 //             y = beta*y + alpha*ff*(sum + mu*x) (grad: the three outputs of nfft_interface.c:547-549)
 //             in one coalesced pass.
+// The interpolation has five kernels.  The plain k_interp, k_interp_hl (H staged in LDS group by group), k_interp_fg
+// (below) and k_interp_part (a row shard's split finish) stand around one set of device helpers: tile_at (the walk
+// over a workgroup's tiles), gather_h / gather_h_lds (a run's coefficients), interp_run (the Horner chain and LDS
+// add of every slot of a run) and ep_prefetch / ep_plain / ep_dot_finish (the epilogue); they differ in where H comes
+// from and in what surrounds the run loop, not in its arithmetic.  k_interp<GRAD> and k_interp2 (two polynomials per
+// slot) keep their own text: on the helpers they measured 8 % and 21 % slower at n = 1e7 x 64
+// (profiles/interp_refactor_ab.txt).
 // The plain matvec of a handle with few blocks runs in two launches (launch_matvec_fused): k_interp_fg does k_grid's
 // work in every workgroup's prologue, for the 33 cells that hold points, and reads H from LDS.
 // Rejected experiments (persistent workgroups, prefetching runs, three-deep run rings, mixed-precision moments,
@@ -128,7 +135,7 @@ __device__ __forceinline__ V* at_off(V* base, uint32_t byte_off)
 }
 
 // the double at LDS byte address `byte_off`: the first dynamic slice of a kernel WITHOUT static LDS starts at LDS
-// address 0 (the launchers check that the kernel's static LDS is 0 bytes: static_lds_zero).  Through the extern
+// address 0 (the launchers check that the kernel's static LDS is 0 bytes: lds_ready).  Through the extern
 // __shared__ pointer the compiler adds the slice base (a link-time constant) to every per-point offset, one VALU
 // add per point
 typedef __attribute__((address_space(3))) double lds_f64;
@@ -211,6 +218,108 @@ __device__ __forceinline__ uint32_t det_interp_exp(const double* __restrict__ hb
    for (int c = 0; c < nw; c++) Y += hb[c];
    const uint32_t bY = ((uint32_t)__double2hiint(Y) >> 20) & 0x7FFu;
    return min(bY + 2u, 2046u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the interpolation kernels' shared pieces
+// ------------------------------------------------------------------------------------------------
+// A wave's walk over the tiles [t0, t1) of its workgroup, wave w taking t0 + w, t0 + w + nwaves, ...:
+//    int t = tile_at(cur, .., t0 + wave, t1);  (prologue)  for (; t < t1; t = tile_at(cur, .., t + nwaves, t1)) ...
+// loads tile t's records if there is such a tile: the first tile's before the caller's prologue, which runs behind
+// the loads, and each next tile's after the current one's evaluation.  Returns t.
+template <int REC>
+__device__ __forceinline__ int tile_at(TileRegs& cur, const uint16_t* __restrict__ meta,
+                                       const uint32_t* __restrict__ lo, const uint32_t* __restrict__ qarr, int t, int t1)
+{
+   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, threadIdx.x & 63);
+   return t;
+}
+
+// a run's kNC coefficients from the global table H[comp][cell][kNC] (mt: the tile's meta, comp << 6 | cell)
+__device__ __forceinline__ void gather_h(double (&h)[kNC], const double* __restrict__ H, uint32_t mt)
+{
+   const double2* src = reinterpret_cast<const double2*>(H + (size_t)mt * kNC);
+#pragma unroll
+   for (int d = 0; d < kNC; d += 2) {
+      const double2 v = src[d / 2];
+      h[d] = v.x;
+      h[d + 1] = v.y;
+   }
+}
+// the same from an LDS table whose degrees lie `stride` doubles apart
+__device__ __forceinline__ void gather_h_lds(double (&h)[kNC], const double* row, int stride)
+{
+#pragma unroll
+   for (int d = 0; d < kNC; d++) h[d] = row[d * stride];
+}
+
+// One run (the kR slots of a lane's tile): per slot the decode, the Horner chain in fma(v, u, h[d]) order and the
+// ds_add_f64 into the LDS y slice, the kernel's first dynamic slice (DET: rounded on the grid C, det_interp_exp)
+template <int REC, bool DET>
+__device__ __forceinline__ void interp_run(const TileRegs& cur, const double (&h)[kNC], double C)
+{
+#pragma unroll
+   for (int r = 0; r < kR; r++) {
+      const uint32_t off = slot_off<REC>(cur, r);
+      const double u = q_to_s(cur.qq[r]);
+      double v = h[kNC - 1];
+#pragma unroll
+      for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, h[d]);
+      lds_add(off, DET ? det_round(v, C) : v);
+   }
+}
+
+// The epilogue of a block, y = beta y + alpha f^2 (s_y + mu x), in one coalesced pass: a thread holds the values
+// j = tid + k THREADS, k < kEpMax, in registers.  Every block fits: B <= kMaxBlock, which NFFT4GP_AMD_BLOCK is
+// clamped to (nfft_api.cpp) and beyond which layout_gpu.hip and Nfft4GPAmdLayoutBuild refuse to build.
+constexpr int kEpMax = 8;
+
+// x (the mu term) and, when beta != 0, y of this thread's values: issued early, behind the run loop
+template <int THREADS>
+__device__ __forceinline__ void ep_prefetch(double (&xe)[kEpMax], double (&ye)[kEpMax], const double* __restrict__ x,
+                                            const double* __restrict__ y, int base, int nloc, double beta)
+{
+   static_assert(kMaxBlock <= kEpMax * THREADS, "a block's epilogue values fit the threads' registers");
+#pragma unroll
+   for (int k = 0; k < kEpMax; k++) {
+      const int j = threadIdx.x + k * THREADS;
+      xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
+      ye[k] = (beta != 0.0 && j < nloc) ? y[(size_t)base + j] : 0.0;
+   }
+}
+
+// the plain epilogue; DOT: returns this thread's part of (y_out, x)
+template <int THREADS, bool DOT>
+__device__ __forceinline__ double ep_plain(const double (&xe)[kEpMax], const double (&ye)[kEpMax], const double* s_y,
+                                           double* __restrict__ y, int base, int nloc, double alpha, double beta,
+                                           double f, double mu)
+{
+   const double ff = f * f;
+   double dacc = 0.0;
+#pragma unroll
+   for (int k = 0; k < kEpMax; k++) {
+      const int j = threadIdx.x + k * THREADS;
+      if (j >= nloc) break;
+      const double v = ff * (s_y[j] + mu * xe[k]);
+      const double yo = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
+      y[(size_t)base + j] = yo;
+      if (DOT) dacc = fma(yo, xe[k], dacc);
+   }
+   return dacc;
+}
+
+// the fused dot's finish: the block's sum, then the deterministic grid-wide sum, written to *dot_out by the last
+// block (reduce.hpp).  s_scr: kRedScratch bytes of dynamic LDS (the kernels keep no static LDS)
+template <int THREADS>
+__device__ __forceinline__ void ep_dot_finish(double dacc, double* s_scr, double* __restrict__ dot_part,
+                                              unsigned int* __restrict__ dot_ticket, double* __restrict__ dot_out)
+{
+   dacc = block_sum0_s<THREADS>(dacc, s_scr);
+   double tot;
+   if (grid_total_s<THREADS>(dacc, dot_part, dot_ticket, &tot, reinterpret_cast<int*>(s_scr + 2 * (THREADS / 64)),
+                             s_scr + THREADS / 64) &&
+       threadIdx.x == 0)
+      *dot_out = tot;
 }
 
 // The fold of one window on the matrix unit (v_mfma_f64_16x16x4_f64), by one wave: G = C M, a 10 x 8 by 8 x 64
@@ -727,39 +836,22 @@ __global__ __launch_bounds__(THREADS) void k_interp_part(const uint16_t* __restr
                                                         double scale)
 {
    extern __shared__ __attribute__((aligned(16))) double smem[];
-   double* s_y = smem;
+   double* s_y = smem;  // the first dynamic slice (lds_add addresses it absolutely)
    const int b = blockIdx.x / S, part = blockIdx.x % S;
    const int g0 = part * ngroups / S, g1 = (part + 1) * ngroups / S;
-   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   constexpr int nwaves = THREADS / 64;
+   const int tid = threadIdx.x;
    const int base = b * B;
    const int nloc = min(B, n - base);
-   const int t1 = tile_off[b * ngroups + g1];
-   int t = tile_off[b * ngroups + g0] + wave;
+   // the tiles of the part's groups, not of the whole block
    TileRegs cur;
-   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
+   const int t1 = tile_off[b * ngroups + g1];
+   int t = tile_at<REC>(cur, meta, lo, qarr, tile_off[b * ngroups + g0] + (tid >> 6), t1);
    for (int i = tid; i < B + kPad; i += THREADS) s_y[i] = 0.0;
    __syncthreads();
-   for (; t < t1; t += nwaves) {
-      const size_t hoff = (size_t)cur.mt * kNC;
-      double hc[kNC];
-#pragma unroll
-      for (int d = 0; d < kNC; d += 2) {
-         const double2 v = *reinterpret_cast<const double2*>(H + hoff + d);
-         hc[d] = v.x;
-         hc[d + 1] = v.y;
-      }
-#pragma unroll
-      for (int r = 0; r < kR; r++) {
-         const uint32_t off = slot_off<REC>(cur, r);
-         const double u = q_to_s(cur.qq[r]);
-         double v = hc[kNC - 1];
-#pragma unroll
-         for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
-         lds_add(off, v);  // s_y is the first dynamic slice
-      }
-      const int tn = t + nwaves;
-      if (tn < t1) load_tile<REC>(cur, meta, lo, qarr, tn, lane);
+   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + THREADS / 64, t1)) {
+      double h[kNC];
+      gather_h(h, H, cur.mt);
+      interp_run<REC, false>(cur, h, 0.0);
    }
    __syncthreads();
    for (int j = tid; j < nloc; j += THREADS) atomicAdd(y + (size_t)base + j, scale * s_y[j]);
@@ -787,10 +879,8 @@ __global__ __launch_bounds__(kGridThreads) void k_reduce_parts(const double* __r
 // ------------------------------------------------------------------------------------------------
 // interpolation + epilogue
 // ------------------------------------------------------------------------------------------------
-constexpr int kEpMax = 8;  // epilogue values per thread held in registers (B <= kEpMax * THREADS)
-
 // DOT (non-GRAD only): also forms (y_out, x) -- the (q, p) of a CG step when y = A p -- with a
-// deterministic grid-wide sum written to *dot_out by the last block (reduce.hpp)
+// deterministic grid-wide sum written to *dot_out by the last block (ep_dot_finish)
 // DET: the y adds rounded on the grid of det_interp_exp (hb: the bounds of H, and of Hd at hb + nw)
 template <bool GRAD, int THREADS, bool DOT = false, bool DET = false, int REC = 5>
 __global__ __launch_bounds__(THREADS) void k_interp(
@@ -802,95 +892,85 @@ __global__ __launch_bounds__(THREADS) void k_interp(
 {
    extern __shared__ __attribute__((aligned(16))) double smem[];
    const int Bp = B + kPad;
-   double* s_y = smem;
+   double* s_y = smem;        // the first dynamic slice (lds_add addresses it absolutely)
    double* s_yd = smem + Bp;  // GRAD only
    const int b = blockIdx.x;
    const int tid = threadIdx.x;
    const int base = b * B;
    const int nloc = min(B, n - base);
-   const int lane = tid & 63;
-   const int wave = tid >> 6;
-   constexpr int nwaves = THREADS / 64;
-   const int t0 = tile_off[b * ngroups];
-   const int t1 = tile_off[(b + 1) * ngroups];
-   TileRegs cur;
-   int t = t0 + wave;
-   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
-   // the epilogue's x (mu term) and, when beta != 0, y are fetched now, behind the first run
-   const bool ep_regs = B <= kEpMax * THREADS;
-   double xe[kEpMax], ye[kEpMax];
-   if (ep_regs) {
+   if constexpr (GRAD) {
+      // The gradient instantiations keep the parent's text and compile to the parent's assembly: on the shared helpers
+      // k_interp<true, 512, false, false, 5> measured 8 % slower at n = 1e7 x 64 and the cause was not found
+      // (profiles/interp_refactor_ab.txt).  Each of these alone moves the assembly, so none is done here: stepping
+      // the walk with tile_at, gather_h for H and Hd, the output triple written once (as a lambda), and removing the
+      // run-time ep_regs test with its strided fallback, which no plan can reach (ep_prefetch)
+      const int lane = tid & 63;
+      const int wave = tid >> 6;
+      constexpr int nwaves = THREADS / 64;
+      const int t0 = tile_off[b * ngroups];
+      const int t1 = tile_off[(b + 1) * ngroups];
+      TileRegs cur;
+      int t = tile_at<REC>(cur, meta, lo, qarr, t0 + wave, t1);
+      // the epilogue's x (mu term) is fetched now, behind the first run
+      const bool ep_regs = B <= kEpMax * THREADS;
+      double xe[kEpMax];
+      if (ep_regs) {
 #pragma unroll
-      for (int k = 0; k < kEpMax; k++) {
-         const int j = tid + k * THREADS;
-         xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
-         ye[k] = (!GRAD && beta != 0.0 && j < nloc) ? y[(size_t)base + j] : 0.0;
+         for (int k = 0; k < kEpMax; k++) {
+            const int j = tid + k * THREADS;
+            xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
+         }
       }
-   }
-   for (int i = tid; i < Bp; i += THREADS) {
-      s_y[i] = 0.0;
-      if (GRAD) s_yd[i] = 0.0;
-   }
-   double Cy = 0.0, Cyd = 0.0;
-   if (DET) {
-      Cy = det_grid(det_interp_exp(hb, nw));
-      if (GRAD) Cyd = det_grid(det_interp_exp(hb + nw, nw));
-   }
-   __syncthreads();
+      for (int i = tid; i < Bp; i += THREADS) {
+         s_y[i] = 0.0;
+         s_yd[i] = 0.0;
+      }
+      const double Cy = DET ? det_grid(det_interp_exp(hb, nw)) : 0.0;
+      const double Cyd = DET ? det_grid(det_interp_exp(hb + nw, nw)) : 0.0;
+      __syncthreads();
 
-   for (; t < t1; t += nwaves) {
-      const int tn = t + nwaves;
-      const size_t hoff = (size_t)cur.mt * kNC;  // (comp*64 + cell) * kNC: meta is comp<<6|cell
-      double hc[kNC], hdc[GRAD ? kNC : 1];
+      for (; t < t1; t += nwaves) {
+         const int tn = t + nwaves;
+         const size_t hoff = (size_t)cur.mt * kNC;  // (comp*64 + cell) * kNC: meta is comp<<6|cell
+         double hc[kNC], hdc[kNC];
 #pragma unroll
-      for (int d = 0; d < kNC; d += 2) {
-         const double2 v = *reinterpret_cast<const double2*>(H + hoff + d);
-         hc[d] = v.x;
-         hc[d + 1] = v.y;
-         if (GRAD) {
+         for (int d = 0; d < kNC; d += 2) {
+            const double2 v = *reinterpret_cast<const double2*>(H + hoff + d);
+            hc[d] = v.x;
+            hc[d + 1] = v.y;
             const double2 vd = *reinterpret_cast<const double2*>(Hd + hoff + d);
             hdc[d] = vd.x;
             hdc[d + 1] = vd.y;
          }
-      }
 #pragma unroll
-      for (int r = 0; r < kR; r++) {
-         const uint32_t off = slot_off<REC>(cur, r);
-         const double u = q_to_s(cur.qq[r]);
-         double v = hc[kNC - 1];
+         for (int r = 0; r < kR; r++) {
+            const uint32_t off = slot_off<REC>(cur, r);
+            const double u = q_to_s(cur.qq[r]);
+            double v = hc[kNC - 1];
 #pragma unroll
-         for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
-         lds_add(off, DET ? det_round(v, Cy) : v);  // s_y is the first dynamic slice
-         if (GRAD) {
+            for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
+            lds_add(off, DET ? det_round(v, Cy) : v);  // s_y is the first dynamic slice
             double vd = hdc[kNC - 1];
 #pragma unroll
             for (int d = kNC - 2; d >= 0; d--) vd = fma(vd, u, hdc[d]);
             lds_add(off + 8u * (uint32_t)Bp, DET ? det_round(vd, Cyd) : vd);  // s_yd follows it
          }
+         if (tn < t1) load_tile<REC>(cur, meta, lo, qarr, tn, lane);
       }
-      if (tn < t1) load_tile<REC>(cur, meta, lo, qarr, tn, lane);
-   }
-   __syncthreads();
+      __syncthreads();
 
-   const double ff = f * f;
-   double dacc = 0.0;
-   double* y0 = y;
-   double* y1 = y + n;
-   double* y2 = y + 2 * (size_t)n;
+      const double ff = f * f;
+      double* y0 = y;
+      double* y1 = y + n;
+      double* y2 = y + 2 * (size_t)n;
 #pragma unroll
-   for (int k = 0; k < kEpMax; k++) {
-      // registers path: k-th value of this thread; fallback (B > kEpMax*THREADS): strided loop below
-      if (!ep_regs) break;
-      const int j = tid + k * THREADS;
-      if (j >= nloc) break;
-      const size_t gj = (size_t)base + j;
-      const double xj = xe[k];
-      if (!GRAD) {
-         const double v = ff * (s_y[j] + mu * xj);
-         const double yo = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
-         y[gj] = yo;
-         if (DOT) dacc = fma(yo, xj, dacc);
-      } else {
+      for (int k = 0; k < kEpMax; k++) {
+         // registers path: k-th value of this thread; fallback (B > kEpMax*THREADS): strided loop below
+         if (!ep_regs) break;
+         const int j = tid + k * THREADS;
+         if (j >= nloc) break;
+         const size_t gj = (size_t)base + j;
+         const double xj = xe[k];
          // nfft_interface.c:547-549 summed over windows: (2f)(Kx + mu x), ff*dscale*K'x, ff*x
          const double v0 = 2.0 * f * (s_y[j] + mu * xj);
          const double v1 = ff * s_yd[j];
@@ -905,20 +985,13 @@ __global__ __launch_bounds__(THREADS) void k_interp(
             y2[gj] = fma(beta, y2[gj], alpha * v2);
          }
       }
-   }
-   if (!ep_regs) {
-      for (int j = tid; j < nloc; j += THREADS) {
-         const size_t gj = (size_t)base + j;
-         const double xj = x[gj];
-         if (!GRAD) {
-            const double v = ff * (s_y[j] + mu * xj);
-            const double yo = (beta == 0.0) ? alpha * v : fma(beta, y[gj], alpha * v);
-            y[gj] = yo;
-            if (DOT) dacc = fma(yo, xj, dacc);
-         } else {
+      if (!ep_regs) {
+         for (int j = tid; j < nloc; j += THREADS) {
+            const size_t gj = (size_t)base + j;
+            const double xj = x[gj];
             const double v0 = 2.0 * f * (s_y[j] + mu * xj);
             const double v1 = ff * s_yd[j];
-            const double v2 = dg * ff * xj;  // dg: 0 on component shards without the diagonal
+            const double v2 = dg * ff * xj;
             if (beta == 0.0) {
                y0[gj] = alpha * v0;
                y1[gj] = alpha * v1;
@@ -930,18 +1003,27 @@ __global__ __launch_bounds__(THREADS) void k_interp(
             }
          }
       }
+      return;
    }
-   if (DOT && !GRAD) {
-      // LDS scratch after the y slices (kRedScratch bytes): the kernel keeps no static LDS (lds_add addresses its
-      // first dynamic slice absolutely)
-      double* s_scr = smem + (GRAD ? 2 : 1) * Bp;
-      dacc = block_sum0_s<THREADS>(dacc, s_scr);
-      double tot;
-      if (grid_total_s<THREADS>(dacc, dot_part, dot_ticket, &tot, reinterpret_cast<int*>(s_scr + 2 * (THREADS / 64)),
-                                s_scr + THREADS / 64) &&
-          threadIdx.x == 0)
-         *dot_out = tot;
+   TileRegs cur;
+   const int t1 = tile_off[(b + 1) * ngroups];
+   int t = tile_at<REC>(cur, meta, lo, qarr, tile_off[b * ngroups] + (tid >> 6), t1);
+   // the epilogue's values are fetched now, behind the first run
+   double xe[kEpMax], ye[kEpMax];
+   ep_prefetch<THREADS>(xe, ye, x, y, base, nloc, beta);
+   for (int i = tid; i < Bp; i += THREADS) s_y[i] = 0.0;
+   const double Cy = DET ? det_grid(det_interp_exp(hb, nw)) : 0.0;
+   __syncthreads();
+
+   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + THREADS / 64, t1)) {
+      double h[kNC];
+      gather_h(h, H, cur.mt);
+      interp_run<REC, DET>(cur, h, Cy);
    }
+   __syncthreads();
+
+   const double dacc = ep_plain<THREADS, DOT>(xe, ye, s_y, y, base, nloc, alpha, beta, f, mu);
+   if (DOT) ep_dot_finish<THREADS>(dacc, smem + Bp, dot_part, dot_ticket, dot_out);  // scratch after the y slice
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -956,9 +1038,10 @@ __global__ __launch_bounds__(THREADS) void k_interp(
 // leave group g (an LDS counter per group) stages group g + 2 into g's slot and publishes it (ready[slot] = g + 2,
 // release), and a wave entering group g >= 2 waits for that (acquire, s_sleep, bounded).  A wave waits only for a
 // group every wave has left two groups before, and the stager stages before it waits for anything, so the waves
-// never wait on one another in a cycle.  Same arithmetic as k_interp's plain path (bitwise equal results).
+// never wait on one another in a cycle.  The runs go through interp_run and the epilogue through ep_plain, as
+// k_interp's plain path (bitwise equal results).
 constexpr int kHlWin = kNC * kNos + 1;
-constexpr size_t kMaxDynamicLds = 160 * 1024;  // a workgroup's LDS on gfx950 (raise_lds_limit_once)
+constexpr size_t kMaxDynamicLds = 160 * 1024;  // a workgroup's LDS on gfx950 (lds_ready)
 
 __host__ __device__ constexpr size_t hl_lds_bytes(int B, int CG, int ngroups, int ns)
 {
@@ -1011,21 +1094,11 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
    const int wave = tid >> 6;
    constexpr int nwaves = THREADS / 64;
    const int gbase = b * ngroups;
-   const int t0 = tile_off[gbase];
-   const int t1 = tile_off[gbase + ngroups];
    TileRegs cur;
-   int t = t0 + wave;
-   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
-   const bool ep_regs = B <= kEpMax * THREADS;
+   const int t1 = tile_off[gbase + ngroups];
+   int t = tile_at<REC>(cur, meta, lo, qarr, tile_off[gbase] + wave, t1);
    double xe[kEpMax], ye[kEpMax];
-   if (ep_regs) {
-#pragma unroll
-      for (int k = 0; k < kEpMax; k++) {
-         const int j = tid + k * THREADS;
-         xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
-         ye[k] = (beta != 0.0 && j < nloc) ? y[(size_t)base + j] : 0.0;
-      }
-   }
+   ep_prefetch<THREADS>(xe, ye, x, y, base, nloc, beta);
    for (int i = tid; i < Bp; i += THREADS) s_y[i] = 0.0;
    for (int i = tid; i < ngroups; i += THREADS) s_done[i] = 0;
    for (int i = tid; i <= ngroups; i += THREADS) s_toff[i] = tile_off[gbase + i];
@@ -1049,7 +1122,7 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
          if (lane == 0) __hip_atomic_store(s_ready + sl, gl + ns, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
    };
-   for (; t < t1; t += nwaves) {
+   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + nwaves, t1)) {
       while (t >= gend) {
          leave(g);
          g++;
@@ -1064,40 +1137,14 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
       }
       const int cl = (int)(cur.mt >> 6) - g * CG;
       const int cell = (int)(cur.mt & 63u);
-      const double* hrow = s_H + ((size_t)gslot * CG + cl) * kHlWin + cell;
-      double hc[kNC];
-#pragma unroll
-      for (int d = 0; d < kNC; d++) hc[d] = hrow[d * kNos];
-#pragma unroll
-      for (int r = 0; r < kR; r++) {
-         const uint32_t off = slot_off<REC>(cur, r);
-         const double u = q_to_s(cur.qq[r]);
-         double v = hc[kNC - 1];
-#pragma unroll
-         for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
-         lds_add(off, DET ? det_round(v, Cy) : v);
-      }
-      if (t + nwaves < t1) load_tile<REC>(cur, meta, lo, qarr, t + nwaves, lane);
+      double h[kNC];
+      gather_h_lds(h, s_H + ((size_t)gslot * CG + cl) * kHlWin + cell, kNos);
+      interp_run<REC, DET>(cur, h, Cy);
    }
    for (; g < ngroups; g++) leave(g);  // the groups this wave has no (more) tiles in
    __syncthreads();
 
-   const double ff = f * f;
-#pragma unroll
-   for (int k = 0; k < kEpMax; k++) {
-      if (!ep_regs) break;
-      const int j = tid + k * THREADS;
-      if (j >= nloc) break;
-      const double v = ff * (s_y[j] + mu * xe[k]);
-      y[(size_t)base + j] = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
-   }
-   if (!ep_regs) {
-      for (int j = tid; j < nloc; j += THREADS) {
-         const size_t gj = (size_t)base + j;
-         const double v = ff * (s_y[j] + mu * x[gj]);
-         y[gj] = (beta == 0.0) ? alpha * v : fma(beta, y[gj], alpha * v);
-      }
-   }
+   ep_plain<THREADS, false>(xe, ye, s_y, y, base, nloc, alpha, beta, f, mu);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1119,7 +1166,7 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
 //      (9, 8, 8, 8): successive cells share 9 of their 10 h values, so 18 LDS reads feed up to 90 FMAs.
 // No workgroup waits for another: the sums were complete when the spread ended.  Block 0 also zeroes gclear, the sum
 // buffer the NEXT fused matvec's spread adds into (its last reader was the previous matvec's interpolation, which
-// stream order has finished).  The run loop and the epilogue are k_interp's plain path.
+// stream order has finished).  The run loop calls interp_run and the epilogue ep_plain, as k_interp's plain path.
 constexpr int kFgWin = kNC * kFgCells + 1;
 constexpr int kFgRow = kNos + 1;          // a staged 64-entry row of g or w
 constexpr int kFgQuads = (kFgSpan + 3) / 4;  // 11 output quads cover the span
@@ -1148,14 +1195,9 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
    const int tid = threadIdx.x;
    const int base = b * B;
    const int nloc = min(B, n - base);
-   const int lane = tid & 63;
-   const int wave = tid >> 6;
-   constexpr int nwaves = THREADS / 64;
-   const int t0 = tile_off[b * ngroups];
-   const int t1 = tile_off[(b + 1) * ngroups];
    TileRegs cur;
-   int t = t0 + wave;
-   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
+   const int t1 = tile_off[(b + 1) * ngroups];
+   int t = tile_at<REC>(cur, meta, lo, qarr, tile_off[b * ngroups] + (tid >> 6), t1);
    // this thread's column of the tap table for step 3, fetched with the first tile (d = tid % 8 for every window)
    double ct[kTaps];
 #pragma unroll
@@ -1214,69 +1256,20 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
    __syncthreads();
    // the epilogue's x (mu term) and, when beta != 0, y are fetched now, behind the run loop: after the build, whose
    // registers they would otherwise share, and after its barrier, which would wait for them
-   const bool ep_regs = B <= kEpMax * THREADS;
    double xe[kEpMax], ye[kEpMax];
-   if (ep_regs) {
-#pragma unroll
-      for (int k = 0; k < kEpMax; k++) {
-         const int j = tid + k * THREADS;
-         xe[k] = (j < nloc) ? x[(size_t)base + j] : 0.0;
-         ye[k] = (beta != 0.0 && j < nloc) ? y[(size_t)base + j] : 0.0;
-      }
-   }
+   ep_prefetch<THREADS>(xe, ye, x, y, base, nloc, beta);
 
-   for (; t < t1; t += nwaves) {
-      const int tn = t + nwaves;
+   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + THREADS / 64, t1)) {
       // meta is comp << 6 | cell; a cell outside the 33 cannot occur (pick_fused_grid), the min keeps the read in s_H
       const int ci = min((int)((cur.mt + 16u) & 63u), kFgCells - 1);
-      const double* hrow = s_H + (size_t)(cur.mt >> 6) * kFgWin + ci;
-      double hc[kNC];
-#pragma unroll
-      for (int d = 0; d < kNC; d++) hc[d] = hrow[d * kFgCells];
-#pragma unroll
-      for (int r = 0; r < kR; r++) {
-         const uint32_t off = slot_off<REC>(cur, r);
-         const double u = q_to_s(cur.qq[r]);
-         double v = hc[kNC - 1];
-#pragma unroll
-         for (int d = kNC - 2; d >= 0; d--) v = fma(v, u, hc[d]);
-         lds_add(off, v);  // s_y is the first dynamic slice
-      }
-      if (tn < t1) load_tile<REC>(cur, meta, lo, qarr, tn, lane);
+      double h[kNC];
+      gather_h_lds(h, s_H + (size_t)(cur.mt >> 6) * kFgWin + ci, kFgCells);
+      interp_run<REC, false>(cur, h, 0.0);
    }
    __syncthreads();
 
-   const double ff = f * f;
-   double dacc = 0.0;
-#pragma unroll
-   for (int k = 0; k < kEpMax; k++) {
-      if (!ep_regs) break;
-      const int j = tid + k * THREADS;
-      if (j >= nloc) break;
-      const double xj = xe[k];
-      const double v = ff * (s_y[j] + mu * xj);
-      const double yo = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
-      y[(size_t)base + j] = yo;
-      if (DOT) dacc = fma(yo, xj, dacc);
-   }
-   if (!ep_regs) {
-      for (int j = tid; j < nloc; j += THREADS) {
-         const size_t gj = (size_t)base + j;
-         const double xj = x[gj];
-         const double v = ff * (s_y[j] + mu * xj);
-         const double yo = (beta == 0.0) ? alpha * v : fma(beta, y[gj], alpha * v);
-         y[gj] = yo;
-         if (DOT) dacc = fma(yo, xj, dacc);
-      }
-   }
-   if (DOT) {
-      dacc = block_sum0_s<THREADS>(dacc, s_scr);
-      double tot;
-      if (grid_total_s<THREADS>(dacc, dot_part, dot_ticket, &tot, reinterpret_cast<int*>(s_scr + 2 * (THREADS / 64)),
-                                s_scr + THREADS / 64) &&
-          threadIdx.x == 0)
-         *dot_out = tot;
-   }
+   const double dacc = ep_plain<THREADS, DOT>(xe, ye, s_y, y, base, nloc, alpha, beta, f, mu);
+   if (DOT) ep_dot_finish<THREADS>(dacc, s_scr, dot_part, dot_ticket, dot_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1292,6 +1285,9 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
 // y_v = beta y_v + alpha f^2 (sum_windows interp_v + mu x_v), v = 0, 1; H of vector v at H + v * h_rs
 // DET: as k_interp's, each vector on the grid of its own bounds (hb, hb + 2 nw: k_grid's per-vector layout), so
 // each column equals the single-vector matvec bit for bit
+// Keeps its own run loop and epilogue (only the first tile's load goes through tile_at): on the shared helpers
+// k_interp2<1024, false, 4> measured 21 % slower at n = 1e7 x 64, cause not found (profiles/interp_refactor_ab.txt),
+// and gather_h for the two tables or tile_at in the loop's step moves the assembly; as written it is the parent's
 template <int THREADS, bool DET = false, int REC = 5>
 __global__ __launch_bounds__(THREADS) void k_interp2(const uint16_t* __restrict__ meta,
                                                      const uint32_t* __restrict__ lo,
@@ -1317,8 +1313,7 @@ __global__ __launch_bounds__(THREADS) void k_interp2(const uint16_t* __restrict_
    const int t0 = tile_off[b * ngroups];
    const int t1 = tile_off[(b + 1) * ngroups];
    TileRegs cur;
-   int t = t0 + wave;
-   if (t < t1) load_tile<REC>(cur, meta, lo, qarr, t, lane);
+   int t = tile_at<REC>(cur, meta, lo, qarr, t0 + wave, t1);
    for (int i = tid; i < Bp; i += THREADS) s_y0[i] = s_y1[i] = 0.0;
    double C0 = 0.0, C1 = 0.0;
    if (DET) {
@@ -1493,14 +1488,6 @@ static InterpFgFn interp_fg_fn(bool dot, int rec)
    return dot ? k_interp_fg<kInterpThreads, true, 5> : k_interp_fg<kInterpThreads, false, 5>;
 }
 
-// a kernel whose dynamic slice is addressed absolutely (lds_at) must have no static LDS
-static bool static_lds_zero(const void* fn)
-{
-   hipFuncAttributes a;
-   if (hipFuncGetAttributes(&a, fn) != hipSuccess) return false;
-   return a.sharedSizeBytes == 0;
-}
-
 // every interpolation kernel the launchers pick
 typedef void (*InterpHlFn)(const uint16_t*, const uint32_t*, const uint32_t*, const int*, const double*, const double*,
                            double*, int, int, int, int, int, double, double, double, double, const double*, int);
@@ -1576,28 +1563,20 @@ static std::vector<const void*> spread_kernels()
    return v;
 }
 
-static void raise_lds_limit_once()
-{
-   // a function-local static initialiser runs once (thread-safe)
-   static const bool raised = []() {
-      for (const void* f : spread_kernels())
-         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
-      for (const void* f : interp_kernels())
-         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
-      (void)hipGetLastError();
-      return true;
-   }();
-   (void)raised;
-}
-
-// every kernel that addresses its dynamic LDS absolutely (lds_at / lds_add) has no static LDS
-static bool abs_lds_ok()
+// Heads every launcher of a spread or interpolation kernel.  Once per process (a function-local static initialiser
+// runs once, thread-safe): the kernels may ask for a workgroup's whole LDS, and every one of them, which addresses
+// its dynamic LDS absolutely (lds_at / lds_add), has no static LDS
+static bool lds_ready()
 {
    static const bool ok = [] {
       std::vector<const void*> v = interp_kernels();
       for (const void* f : spread_kernels()) v.push_back(f);
       for (const void* f : v)
-         if (!static_lds_zero(f)) return false;
+         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds);
+      (void)hipGetLastError();
+      hipFuncAttributes a;
+      for (const void* f : v)
+         if (hipFuncGetAttributes(&a, f) != hipSuccess || a.sharedSizeBytes != 0) return false;
       return true;
    }();
    if (!ok) fprintf(stderr, "nfft4gp_amd: a matvec kernel has static LDS; its absolute LDS addressing would be wrong\n");
@@ -1608,8 +1587,7 @@ static int launch_spread_to(const AdditivePlan& P, const double* d_x, double* d_
                             hipStream_t stream)
 {
    if (P.dl.ntiles == 0 || P.n == 0) return 0;
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    const SpreadFn fn = spread_fn(P);
    const int gridx = ((P.nblocks + 7) / 8) * 8 * P.ngroups;
    launch_ev(fn, dim3(gridx), dim3(kSpreadThreads), spread_lds_bytes(P), stream, P.kev ? P.kev + 0 : nullptr,
@@ -1637,6 +1615,19 @@ bool grid_atomic(const AdditivePlan& P)
    return v > 0 || P.nblocks <= kAtomicGridMaxBlocks;
 }
 
+// k_grid over the plan's windows, from `nparts` partial grids per window or (from_sum) from the summed grids, which
+// clear_sum zeroes for the next matvec.  H2: the two-vector matvec (not timed), vector v's grids at src + v part_rs
+// and its H at H2 + v h_rs.  Deterministic mode also takes the bounds of H (P.d_hb).
+static int launch_k_grid(const AdditivePlan& P, const double* src, int nparts, int from_sum, int grad, int clear_sum,
+                         hipStream_t stream, double* H2 = nullptr, size_t part_rs = 0, size_t h_rs = 0)
+{
+   launch_ev(k_grid, dim3(P.nw, H2 ? 2 : 1), dim3(kGridThreads), 0, stream, P.kev && !H2 ? P.kev + 2 : nullptr, src,
+             nparts, (const double*)P.d_w, (const double*)P.d_wd, H2 ? H2 : P.d_H, P.d_Hd, grad, from_sum,
+             (long long)part_rs, (long long)h_rs, P.det ? P.d_hb : (double*)nullptr, clear_sum);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   return 0;
+}
+
 int launch_spread_grid(AdditivePlan& P, const double* d_x, int grad, hipStream_t stream)
 {
    if (!grid_atomic(P) || P.nblocks == 0) {
@@ -1648,28 +1639,17 @@ int launch_spread_grid(AdditivePlan& P, const double* d_x, int grad, hipStream_t
       NFFT4GP_HIP_CHECK(hipMemsetAsync(P.d_gsum, 0, sizeof(double) * (size_t)P.nw * kNos, stream));
    }
    if (launch_spread_to(P, d_x, nullptr, P.d_gsum, stream)) return -1;
-   launch_ev(k_grid, dim3(P.nw), dim3(kGridThreads), 0, stream, P.kev ? P.kev + 2 : nullptr, (const double*)P.d_gsum, 1,
-             (const double*)P.d_w, (const double*)P.d_wd, P.d_H, P.d_Hd, grad, 1, 0ll, 0ll, (double*)nullptr, 1);
-   NFFT4GP_HIP_CHECK(hipGetLastError());
-   return 0;
+   return launch_k_grid(P, P.d_gsum, 1, 1, grad, 1, stream);  // not deterministic here (grid_atomic): no bounds
 }
 
 int launch_grid(const AdditivePlan& P, const double* d_part, int nparts, int grad, hipStream_t stream)
 {
-   launch_ev(k_grid, dim3(P.nw), dim3(kGridThreads), 0, stream, P.kev ? P.kev + 2 : nullptr, d_part, nparts,
-             (const double*)P.d_w, (const double*)P.d_wd, P.d_H, P.d_Hd, grad, 0, 0ll, 0ll,
-             P.det ? P.d_hb : (double*)nullptr, 0);
-   NFFT4GP_HIP_CHECK(hipGetLastError());
-   return 0;
+   return launch_k_grid(P, d_part, nparts, 0, grad, 0, stream);
 }
 
 int launch_grid_from_sum(const AdditivePlan& P, const double* d_gridsum, int grad, hipStream_t stream)
 {
-   launch_ev(k_grid, dim3(P.nw), dim3(kGridThreads), 0, stream, P.kev ? P.kev + 2 : nullptr, d_gridsum, 1,
-             (const double*)P.d_w, (const double*)P.d_wd, P.d_H, P.d_Hd, grad, 1, 0ll, 0ll,
-             P.det ? P.d_hb : (double*)nullptr, 0);
-   NFFT4GP_HIP_CHECK(hipGetLastError());
-   return 0;
+   return launch_k_grid(P, d_gridsum, 1, 1, grad, 0, stream);
 }
 
 int launch_shard_finish_split(const AdditivePlan& P, const double* d_gridsum, double alpha, const double* d_x,
@@ -1677,8 +1657,7 @@ int launch_shard_finish_split(const AdditivePlan& P, const double* d_gridsum, do
                               const double* d_part)
 {
    constexpr int T = 512;
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    if (A && A->slot_doubles != (long long)P.nw * kNos) return -1;
    const double ff = P.f * P.f;
    hipLaunchKernelGGL(k_grid_sum_yinit, dim3(P.nw), dim3(kGridThreads), 0, stream, d_gridsum, (const double*)P.d_w,
@@ -1730,8 +1709,7 @@ int launch_interp(const AdditivePlan& P, int grad, double alpha, const double* d
                   hipStream_t stream, double* d_dot)
 {
    if (P.n == 0) return 0;
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    if (d_dot && (grad || P.nblocks > kRedMaxBlocks)) {
       fprintf(stderr, "nfft4gp_amd: fused matvec-dot needs a plain matvec and <= %d blocks\n", kRedMaxBlocks);
       return -1;
@@ -1781,8 +1759,7 @@ bool pick_fused_grid(const AdditivePlan& P)
 int launch_matvec_fused(AdditivePlan& P, double alpha, const double* d_x, double beta, double* d_y, hipStream_t stream,
                         double* d_dot)
 {
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    if (d_dot && P.nblocks > kRedMaxBlocks) return -1;
    const size_t ns = (size_t)P.nw * kNos;
    if (!P.d_hsum) {
@@ -1809,8 +1786,7 @@ int launch_interp_blocks(const AdditivePlan& P, double alpha, const double* d_x,
                          int b1, hipStream_t stream)
 {
    if (P.n == 0 || b1 <= b0) return 0;
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    const size_t off = (size_t)b0 * P.B;
    hipLaunchKernelGGL(interp_fn(false, false, false, P.det, P.rec), dim3(b1 - b0), dim3(kInterpThreads),
                       interp_lds_bytes(P, 0), stream, P.dl.meta, P.dl.lo, P.dl.q, P.dl.tile_off + (size_t)b0 * P.ngroups,
@@ -1829,8 +1805,7 @@ int launch_matvec2(AdditivePlan& P, double alpha, const double* x0, const double
 {
    if (P.n == 0) return 0;
    if (P.md.on) return -1;
-   raise_lds_limit_once();
-   if (!abs_lds_ok()) return -1;
+   if (!lds_ready()) return -1;
    const size_t part_rs = (size_t)std::max(1, P.nparts) * P.nw * kNos;
    const size_t h_rs = (size_t)P.nw * kNos * kNC;
    // both vectors' partial grids in one allocation, so k_grid's per-vector stride stays inside it
@@ -1838,9 +1813,7 @@ int launch_matvec2(AdditivePlan& P, double alpha, const double* x0, const double
    if (!P.d_H2) NFFT4GP_HIP_CHECK(hipMalloc((void**)&P.d_H2, sizeof(double) * 2 * h_rs));
    if (launch_spread(P, x0, P.d_part2, stream) || launch_spread(P, x1, P.d_part2 + part_rs, stream)) return -1;
    // P.d_hb holds [vector][H, Hd][nw]: the grid writes each vector's H bound at hb + 2 nw y
-   hipLaunchKernelGGL(k_grid, dim3(P.nw, 2), dim3(kGridThreads), 0, stream, (const double*)P.d_part2, P.nparts,
-                      (const double*)P.d_w, (const double*)P.d_wd, P.d_H2, P.d_Hd, 0, 0, (long long)part_rs,
-                      (long long)h_rs, P.det ? P.d_hb : (double*)nullptr, 0);
+   if (launch_k_grid(P, P.d_part2, P.nparts, 0, 0, 0, stream, P.d_H2, part_rs, h_rs)) return -1;
    const size_t lds_i = sizeof(double) * 2 * ((size_t)P.B + kPad);
    const bool small = pick_interp2_threads() == 512;
    hipLaunchKernelGGL(interp2_fn(P.det, small, P.rec), dim3(P.nblocks), dim3(small ? 512 : kInterp2Threads), lds_i, stream,

@@ -192,12 +192,12 @@ class NFFTAdditiveKernel:
     # ---- introspection ---------------------------------------------------------------------------
     def layout_info(self) -> dict:
         """The layout's statistics, and what the matvec's launchers pick for this handle as it stands
-        (spread_variant .. fused_grid: include/nfft4gp_amd.h, Nfft4GPAmdAdditiveLayoutInfo)."""
-        out = (C.c_longlong * 17)()
-        _lib.lib().Nfft4GPAmdAdditiveLayoutInfo(self.h, out, 17)
+        (spread_variant .. shard_split: include/nfft4gp_amd.h, Nfft4GPAmdAdditiveLayoutInfo)."""
+        out = (C.c_longlong * 18)()
+        _lib.lib().Nfft4GPAmdAdditiveLayoutInfo(self.h, out, 18)
         keys = ["n", "nwindows", "block", "nblocks", "ntiles", "slots", "R", "comps_per_group", "ngroups",
                 "layout_bytes", "spread_variant", "grid_atomic", "interp_threads", "interp_hl", "hl_slots",
-                "interp2_threads", "fused_grid"]
+                "interp2_threads", "fused_grid", "shard_split"]
         return dict(zip(keys, [int(v) for v in out]))
 
     def set_deterministic(self, on: bool = True):

@@ -73,15 +73,16 @@ def inputs(name):
     return X, x, x2, y0, b
 
 
-def make_op(amd, name, det, bits, env=None):
-    """The case's handle, set up; `env` (and the case's own) is in os.environ only around the constructor."""
+def make_op(amd, name, det, bits, env=None, shard=None):
+    """The case's handle (shard: of the rows [shard[0], shard[1]) only), set up; `env` (and the case's own) is in
+    os.environ only around the constructor."""
     n, d, kernel, case_env, _ = case(name)
     X = inputs(name)[0]
     env = dict(case_env, **(env or {}))
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        op = amd.NFFTAdditiveKernel(X, np.arange(d, dtype=np.int32), d, 1)
+        op = amd.NFFTAdditiveKernel(X, np.arange(d, dtype=np.int32), d, 1, shard=shard)
     finally:
         for k, v in saved.items():
             if v is None:

@@ -37,7 +37,8 @@ no further child is started: the remaining child tests fail at once.  One child 
 
 In this process (per-handle switches): 514 blocks of 256 points -- the 512-thread k_interp plain / GRAD / DOT as
 the launcher itself picks them and k_grid's partial-grid sum over three passes, the last one ragged -- and
-k_spread's variants 3 (PIPE) and 2 (the chain's moment table)."""
+k_spread's variants 3 (PIPE) and 2 (the chain's moment table); and the split finish of two row shards
+(k_interp_part: NFFT4GP_AMD_SHARD_SPLIT, read per call, and layout_info()'s shard_split)."""
 import json
 import os
 import subprocess
@@ -334,3 +335,58 @@ def test_spread_variants(torch_cuda, monkeypatch, oracle_ref, name, variant):
         op0.free()
         bad += [(bits, k, rel(rec[k], rec0[k])) for k in FIELDS if not np.array_equal(rec[k], rec0[k])]
     assert not bad, bad
+
+
+# ---- in this process: the row shards' split finish --------------------------------------------------------------
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("name,S,parts", [("three_groups", 2, [1, 2]), ("three_groups", 3, [1, 1, 1]),
+                                          ("many_groups", 4, [2, 3, 3, 3])])
+def test_shard_split_finish(torch_cuda, monkeypatch, oracle_ref, name, S, parts, bits):
+    """k_interp_part: two row shards (dist.row_range) whose finish runs S workgroups per block, each over a
+    contiguous range of window groups (NFFT4GP_AMD_SHARD_SPLIT, read per call); `parts` is the number of groups
+    per workgroup.  The shards' blocks are 512 points, so that every shard has more than one.  The grids are summed
+    as the all-reduce does (_shard_sum of test_gpu_configs.py); the concatenated rows of the finish with beta = 0
+    onto NaN and with (ALPHA, BETA) are held to the oracle, and with 64-bit records to the whole handle at 1e-12
+    (test_config_d_eight_row_shards_on_one_gpu's bound: the shards start at multiples of 16, so the operator is the
+    whole handle's up to the order of its sums)."""
+    from preconditioned_additive_gaussian_processes_with_fourier_acceleration_amd.dist import row_range
+    torch = torch_cuda
+    free_switches(monkeypatch)
+    n = W.case(name)[0]
+    _, x, _, y0, _ = W.inputs(name)
+    shards = [W.make_op(amd, name, 0, bits, {"NFFT4GP_AMD_BLOCK": "512"}, shard=row_range(n, r, 2)) for r in range(2)]
+    total = torch.zeros(shards[0].shard_grid_size(), dtype=torch.float64, device="cuda")
+    for s in shards:
+        g = torch.zeros_like(total)
+        s.shard_spread(torch.tensor(x[s.row_begin:s.row_end], device="cuda"), g)
+        total += g
+    monkeypatch.setenv("NFFT4GP_AMD_SHARD_SPLIT", str(S))
+    ys, yabs = [], []
+    for s in shards:
+        info = s.layout_info()  # shard_split reads the variable as the finish does
+        ng = GEOMETRY[name]["ngroups"]
+        assert info["shard_split"] == S and info["ngroups"] == ng and info["block"] == 512, info
+        assert info["nblocks"] >= 2 and info["n"] == s.n, info
+        assert [(p + 1) * ng // S - p * ng // S for p in range(S)] == parts
+        xs = torch.tensor(x[s.row_begin:s.row_end], device="cuda")
+        y = torch.full((s.n,), float("nan"), dtype=torch.float64, device="cuda")
+        ys.append(s.shard_finish(total, xs, 1.0, 0.0, y).cpu().numpy())
+        yab = torch.tensor(y0[s.row_begin:s.row_end], device="cuda")
+        yabs.append(s.shard_finish(total, xs, W.ALPHA, W.BETA, yab).cpu().numpy())
+        s.free()
+    monkeypatch.delenv("NFFT4GP_AMD_SHARD_SPLIT")
+    rec = {"y": np.concatenate(ys), "y_ab": np.concatenate(yabs)}
+    ref = oracle_ref(name)
+    e = {k: rel(rec[k], ref[k]) for k in rec}
+    if bits == 64:
+        full = W.make_op(amd, name, 0, bits)
+        xd = torch.tensor(x, device="cuda")
+        e["y_whole"] = rel(rec["y"], full.matsymv(xd).cpu().numpy())
+        yab = full.matsymv(xd, W.ALPHA, W.BETA, torch.tensor(y0, device="cuda"))
+        e["y_ab_whole"] = rel(rec["y_ab"], yab.cpu().numpy())
+        full.free()
+    print(f"{name} S {S} bits {bits}: " + ", ".join(f"{k} {v:.2e}" for k, v in e.items()))
+    assert not np.isnan(rec["y"]).any(), "NaN survives beta = 0"
+    assert max(e["y"], e["y_ab"]) <= (TOL_TIGHT if bits == 64 else TOL_CONTRACT), e
+    if bits == 64:
+        assert max(e["y_whole"], e["y_ab_whole"]) <= 1e-12, e

@@ -1000,6 +1000,14 @@ int Nfft4GPAmdHostLuSolve(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *B, int
 /* the same LU's log|det A| (U's diagonal summed in column order) and the sign of det A; 0, the first zero pivot's
  * column + 1, or -1 */
 int Nfft4GPAmdHostLuLogdet(const NFFT4GP_DOUBLE *A, int n, NFFT4GP_DOUBLE *logabsdet, int *sign);
+/* FGMRES's Givens least-squares recurrence on the host (the one every FGMRES driver uses; no device): a cycle
+ * that starts from the residual norm beta and takes the k columns of the column-major (k + 1) x k upper
+ * Hessenberg H in order.  res (k): the residual estimate after each column; y (k): the back-substituted solution;
+ * *breakdown: the column at which breakdown was reported (the cycle stops there, y is the solution of the columns
+ * before it, the rest of res and y is 0), or -1.  k0 > 0: the same object first runs a cycle on (k0, beta0, H0),
+ * as before a restart.  0, or -1 on bad arguments */
+int Nfft4GPAmdDebugGivensLsq(int k, NFFT4GP_DOUBLE beta, const NFFT4GP_DOUBLE *H, int k0, NFFT4GP_DOUBLE beta0,
+                             const NFFT4GP_DOUBLE *H0, NFFT4GP_DOUBLE *res, NFFT4GP_DOUBLE *y, int *breakdown);
 
 #ifdef __cplusplus
 }

@@ -294,6 +294,7 @@ _SIGS = {
     "Nfft4GPAmdFeatureGpStatus": (C.c_int, [vp, ip, dp]),
     "Nfft4GPAmdFeatureGpFree": (None, [vp]),
     "Nfft4GPAmdHostLuLogdet": (C.c_int, [vp, C.c_int, dp, ip]),
+    "Nfft4GPAmdDebugGivensLsq": (C.c_int, [C.c_int, C.c_double, vp, C.c_int, C.c_double, vp, vp, vp, ip]),
     "Nfft4GPAmdHostTapPoly": (C.c_int, [vp]),
     "Nfft4GPAmdHostCirculant": (C.c_int, [C.c_int, C.c_double, C.c_double, vp, vp]),
     "Nfft4GPAmdHostPrepare": (C.c_double, [vp, C.c_int, vp]),

@@ -20,12 +20,15 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "callbacks.hpp"
+#include "fgmres_lsq.hpp"
 #include "internal.h"
 #include "reduce.hpp"
 
@@ -42,6 +45,24 @@ int kgrid(size_t n)
    size_t g = (n + (size_t)kKThreads * kKEPT - 1) / ((size_t)kKThreads * kKEPT);
    g = std::min<size_t>(g, kKMaxBlocks);
    return (int)(g == 0 ? 1 : g);
+}
+
+// the grid of the 1024-thread x 4-element kernels (k_gs_step, k_gs_batch and the one-launch sweeps)
+unsigned gs_grid(size_t n)
+{
+   return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
+}
+
+// workgroups of 1024 threads of `kernel` that are resident on the device at once (occupancy x CUs); 0: unknown
+template <class K>
+int resident_workgroups(K kernel)
+{
+   int dev = 0, occ = 0;
+   hipDeviceProp_t prop;
+   if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 1024, 0) == hipSuccess)
+      return occ * prop.multiProcessorCount;
+   return 0;
 }
 
 // w -= (*hprev) * u (when u != nullptr); then *out = (w, v) (v != nullptr) or ||w||^2 (v == nullptr).
@@ -978,28 +999,10 @@ struct KScratch {
          NFFT4GP_HIP_CHECK(hipMalloc((void**)&lz_ticket, sizeof(unsigned int) * 3 * kTicketWords));
          NFFT4GP_HIP_CHECK(hipMemset(lz_ticket, 0, sizeof(unsigned int) * 3 * kTicketWords));
       }
-      if (lz_occ < 0) {
-         int dev = 0, occ = 0;
-         hipDeviceProp_t prop;
-         lz_occ = 0;
-         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_local<1024, 4>, 1024, 0) == hipSuccess)
-            lz_occ = occ * prop.multiProcessorCount;
-      }
+      if (lz_occ < 0) lz_occ = resident_workgroups(k_lanczos_local<1024, 4>);
       if (chain_occ < 0) {
-         int dev = 0, occ = 0;
-         hipDeviceProp_t prop;
-         chain_occ = 0;
-         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mgs_chain<1024, 4>, 1024, 0) == hipSuccess)
-            chain_occ = occ * prop.multiProcessorCount;
-         for (int x = 0; x < 6; x++) {
-            wide_occ[x] = 0;
-            occ = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, mgs_wide_fn(kWideS[x]), 1024, 0) == hipSuccess)
-               wide_occ[x] = occ * prop.multiProcessorCount;
-         }
+         chain_occ = resident_workgroups(k_mgs_chain<1024, 4>);
+         for (int x = 0; x < 6; x++) wide_occ[x] = resident_workgroups(mgs_wide_fn(kWideS[x]));
       }
       return 0;
    }
@@ -1022,7 +1025,7 @@ struct Ctx {
    // covers n in S passes), -1 neither (the per-projection chain on its usual grid)
    int mgs_form(unsigned* grid)
    {
-      *grid = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
+      *grid = gs_grid(n);
       if (comm || g_k.ensure_chain()) return -1;
       const char* e = getenv("NFFT4GP_AMD_MGS_WIDE");
       const int forced = e ? atoi(e) : 0;
@@ -1055,12 +1058,22 @@ struct Ctx {
    {
       // 1024 threads x 4 elements: a quarter of the 256-thread partials for the last block to add (8.35 us per
       // projection at n = 1e6 against 9.16; 1024 x 8: 10.7, 512 x 4: 8.49 -- round 3, tools/ab_gs.sh, removed)
-      const unsigned grid =
-          grid_in ? grid_in : (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
+      const unsigned grid = grid_in ? grid_in : gs_grid(n);
       hipLaunchKernelGGL((k_gs_step<1024, 4>), dim3(grid), dim3(1024), 0, s, w, u, hprev, v, n, g_k.part, g_k.ticket,
                          out);
       NFFT4GP_HIP_CHECK(hipGetLastError());
       return red(out, 1);
+   }
+   // the MGS sweep as one launch per projection (w against V[0..i), then ||w||^2) into hd[0..i], on the grid of
+   // the one-launch form this n would take, so the two are bitwise equal; i = 0: the norm only
+   int gs_chain(double* w, const double* V, int i, double* hd)
+   {
+      unsigned mg = 0;
+      if (mgs_form(&mg) < 0) mg = 0;
+      for (int j = 0; j < i; j++)
+         if (gs(w, j ? V + (size_t)(j - 1) * n : nullptr, j ? hd + j - 1 : nullptr, V + (size_t)j * n, hd + j, mg))
+            return -1;
+      return gs(w, i ? V + (size_t)(i - 1) * n : nullptr, i ? hd + i - 1 : nullptr, nullptr, hd + i, mg);
    }
    // the MGS sweep of an FGMRES step (w against V[0..i), then ||w||^2) into hd[0..i] in one launch when the grid
    // fits (k_mgs_chain); returns 1 when it does not (the caller runs the k_gs_step chain)
@@ -1088,7 +1101,7 @@ struct Ctx {
    // otherwise block_gs.  NFFT4GP_AMD_LANCZOS_LOCAL=0 keeps block_gs.
    int lanczos_local(double* w, const double* Vl, const double* Zl, int ml, double* h)
    {
-      const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
+      const unsigned grid = gs_grid(n);
       const char* e = getenv("NFFT4GP_AMD_LANCZOS_LOCAL");
       lz_launched = false;
       if (comm || (e && atoi(e) == 0) || ml < 1 || ml > 2 || g_k.ensure_chain() || (size_t)grid * 4096 < n ||
@@ -1299,6 +1312,96 @@ int tridiag_eig(int m, const double* d, const double* e, std::vector<double>& w,
    return sym_eig_host(A, m, w, V);
 }
 
+// owners of a device buffer, a pinned host buffer and an event: freed on every way out of their scope.  Whoever
+// holds them synchronises the stream first where work may still read them.
+template <class T>
+struct DevBuf {
+   T* p = nullptr;
+   DevBuf() = default;
+   DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+   DevBuf(const DevBuf&) = delete;
+   DevBuf& operator=(const DevBuf&) = delete;
+   ~DevBuf() { (void)hipFree(p); }
+   int alloc(size_t count) { return dmalloc(&p, count); }
+   operator T*() const { return p; }
+};
+
+template <class T>
+struct PinBuf {
+   T* p = nullptr;
+   PinBuf() = default;
+   PinBuf(const PinBuf&) = delete;
+   PinBuf& operator=(const PinBuf&) = delete;
+   ~PinBuf()
+   {
+      if (p) (void)hipHostFree(p);
+   }
+   int alloc(size_t count)
+   {
+      if (hipHostMalloc((void**)&p, sizeof(T) * count) == hipSuccess) return 0;
+      p = nullptr;
+      return -1;
+   }
+   operator T*() const { return p; }
+};
+
+struct EventHold {
+   hipEvent_t e = nullptr;
+   EventHold() = default;
+   EventHold(const EventHold&) = delete;
+   EventHold& operator=(const EventHold&) = delete;
+   ~EventHold()
+   {
+      if (e) (void)hipEventDestroy(e);
+   }
+};
+
+// declared after the owners whose buffers the stream's queued work may still use: it drains before they are freed
+struct SyncOnExit {
+   hipStream_t s;
+   ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// The report lines of the solvers (the reference's printf calls in fgmres.c and lanczos.c): to stdout, or
+// appended to *to (the batch driver prints per system at the end).
+struct Report {
+   std::string* to = nullptr;
+   // the banner, "Start FlexGMRES(kdim)" or "Start Lanczos(maxits)" by name and dim, and the line of step 0
+   void header(const char* name, int dim, double tolr, int maxits, double normr, double rel0) const
+   {
+      const char* rule = "--------------------------------------------------------------------------------\n";
+      put("%s", rule);
+      put("Start %s(%d)\n", name, dim);
+      put("Residual Tol: %e\nMax number of inner iterations: %d\n", tolr, maxits);
+      put("%s", rule);
+      put("Step    Residual norm  Relative res.  Convergence Rate\n");
+      put("%5d   %8e   %8e   N/A\n", 0, normr, rel0);
+   }
+   void step(int iter, double normr, double rel, double rel_prev) const
+   {
+      put("%5d   %8e   %8e   %8.6f\n", iter, normr, rel, rel / rel_prev);
+   }
+   void cycle_end(int kdim, int iter, double rel) const
+   {
+      put("Rel. residual at the end of current cycle (# of steps per cycle/total its: %d/%d): %e \n", kdim, iter, rel);
+   }
+
+private:
+   __attribute__((format(printf, 2, 3))) void put(const char* fmt, ...) const
+   {
+      va_list ap;
+      va_start(ap, fmt);
+      if (to) {
+         char buf[256];
+         vsnprintf(buf, sizeof(buf), fmt, ap);
+         *to += buf;
+      } else {
+         vprintf(fmt, ap);
+      }
+      va_end(ap);
+   }
+};
+
 }  // namespace
 
 namespace nfft4gp_amd {
@@ -1317,6 +1420,93 @@ int fgmres_ortho()
    return g_fgmres_ortho;
 }
 
+// ---- FGMRES on one system: what every orthogonalisation shares -------------------------------------------------
+// One solve's basis V, preconditioned directions Z, residual history and least-squares problem, with the parts of
+// fgmres.c:3-252 that do not depend on how a Hessenberg column is obtained.  Every way out of the solve releases
+// all of it; the history goes to the caller with the results (done) and never otherwise.
+struct FgmresRun {
+   Callbacks& cb;
+   Ctx& c;
+   int print_level;
+   double* prel_res;
+   double** prel_res_v;
+   int* piter;
+   DevBuf<double> V, Z;  // without a preconditioner z_i = v_i: the combination reads V and no Z is kept
+   double* rel = nullptr;
+   double normb = 0.0, normr = 0.0, tolr = 0.0;
+   GivensLsq lsq;
+   std::vector<double> y;  // the coefficients of x += Z y: kept until the stream is synchronised (Ctx::combine copies)
+   Report rep;
+   ~FgmresRun()
+   {
+      (void)hipStreamSynchronize(c.s);
+      free(rel);
+   }
+   int done(double rel_res, int iter)
+   {
+      *prel_res = rel_res;
+      *piter = iter;
+      *prel_res_v = rel ? rel : rel_hist(1);  // (the early exits have no history yet)
+      rel = nullptr;
+      return 0;
+   }
+   // up to the first cycle: ||b||, the basis (kdim at most kmax, the orthogonalisation's limit), r0 = b - A x in
+   // its column 0, the tolerance, the banner.  1: solved already (done was called), -1: error, 0: iterate
+   int begin(double* x, const double* rhs, int kdim, int kmax, int maxits, int atol, double tol)
+   {
+      const size_t n = c.n;
+      const double EPS = DBL_EPSILON;
+      if (cb.n_global == 0) {  // (a row shard may hold no rows: it still takes part in every all-reduce)
+         done(0.0, 0);
+         return 1;
+      }
+      normb = c.norm(rhs);
+      if (normb < EPS) {
+         NFFT4GP_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(double) * n, c.s));
+         done(0.0, 0);
+         return 1;
+      }
+      if (kdim > kmax) {
+         fprintf(stderr, "nfft4gp_amd: Nfft4GPSolverFgmres: restart dimension %d above %d\n", kdim, kmax);
+         return -1;
+      }
+      if (V.alloc(n * (size_t)(kdim + 1)) || (cb.prec && Z.alloc(n * (size_t)(kdim + 1)))) return -1;
+      c.copy(V, rhs);
+      if (cb.apply(-1.0, x, 1.0, V)) return -1;
+      normr = c.norm(V);
+      if (normr < EPS) {
+         done(0.0, 0);
+         return 1;
+      }
+      tolr = atol ? tol : tol * normb;
+      rel = rel_hist(maxits + 1);
+      rel[0] = normr / normb;
+      if (print_level > 0) rep.header("FlexGMRES", kdim, tolr, maxits, normr, rel[0]);
+      return 0;
+   }
+   // the next Hessenberg column of the cycle, at iteration iter (fgmres.c:160-200): the residual estimate, the
+   // history and the step's line; false: breakdown
+   bool push(const double* col, int iter)
+   {
+      if (!lsq.push(col, &normr)) return false;
+      rel[iter] = normr / normb;
+      if (print_level > 0) rep.step(iter, normr, rel[iter], rel[iter - 1]);
+      return true;
+   }
+   void cycle_end(int kdim, int iter)
+   {
+      if (print_level == 0) rep.cycle_end(kdim, iter, rel[iter]);
+   }
+   // restart (fgmres.c:236-243): column 0 = rhs - A x through w
+   int restart(double* x, const double* rhs, double* w)
+   {
+      c.copy(V, rhs);
+      if (cb.apply(1.0, x, 0.0, w)) return -1;
+      hipLaunchKernelGGL(k_sub, dim3(egrid(c.n)), dim3(256), 0, c.s, V.p, (const double*)V.p, (const double*)w, c.n);
+      return 0;
+   }
+};
+
 // ---- FGMRES with DCGS2 (ortho 2) ------------------------------------------------------------------------------
 // The reference's FGMRES (fgmres.c:3-252: the same Givens recurrence, breakdown exit, restart and reporting)
 // with the Arnoldi basis orthogonalised by delayed CGS2 (Swirydowicz, Langou, Ananthan, Yang, Thomas 2020):
@@ -1332,81 +1522,26 @@ int fgmres_ortho()
 // z_j^0 = M^-1 v_j^0 is kept, w = A z_j^0, and the finalised direction z_j = (z_j^0 - sum_{k<j} s_k z_k) / alpha
 // satisfies A z_j = (w - V H s) / alpha: the same Arnoldi relation, so V, H and the sweeps are unchanged.  z_j is
 // never formed: x += Z y is applied as Z^0 c, c from y by the triangular recurrence of the s and alpha (combine).
-int fgmres_dcgs2_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int maxits, int atol, double tol,
-                     double* prel_res, double** prel_res_v, int* piter, int print_level)
+// The cycles of a solve that FgmresRun::begin has started.
+static int fgmres_dcgs2_cycles(FgmresRun& run, double* x, const double* rhs, int kdim, int maxits)
 {
-   const size_t n = cb.n;
-   Ctx c{current_stream(), n, cb.comm};
-   const double EPS = DBL_EPSILON;
-   if (cb.n_global == 0) {
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      return 0;
-   }
-   const double normb = c.norm(rhs);
-   if (normb < EPS) {
-      NFFT4GP_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(double) * n, c.s));
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      return 0;
-   }
-   const int kmax = KScratch::kScal / 2 - 2;
-   if (kdim > kmax) {
-      fprintf(stderr, "nfft4gp_amd: Nfft4GPSolverFgmres: restart dimension %d above %d\n", kdim, kmax);
-      return -1;
-   }
-   double *V = nullptr, *Z = nullptr;  // Z: the provisional directions z_j^0 = M^-1 v_j^0 (preconditioned only)
-   double* rel = nullptr;
-   auto cleanup = [&]() {
-      (void)hipStreamSynchronize(c.s);
-      (void)hipFree(V);
-      (void)hipFree(Z);
-   };
-   // every error exit: the basis, Z and the history are released
-   auto fail = [&]() -> int {
-      free(rel);
-      rel = nullptr;
-      cleanup();
-      return -1;
-   };
-   if (dmalloc(&V, n * (size_t)(kdim + 1)) || (cb.prec && dmalloc(&Z, n * (size_t)(kdim + 1)))) return fail();
-   // Hr: the unrotated Hessenberg (the Arnoldi relation), H: the rotated one (fgmres.c's H)
-   std::vector<double> Hr((size_t)kdim * (kdim + 1), 0.0), H((size_t)kdim * (kdim + 1), 0.0), cs(kdim), sn(kdim),
-       rs(kdim + 1);
+   Callbacks& cb = run.cb;
+   Ctx& c = run.c;
+   const size_t n = c.n;
+   double *V = run.V, *Z = run.Z;  // Z: the provisional directions z_j^0 = M^-1 v_j^0 (preconditioned only)
+   double& normr = run.normr;
+   // Hr: the unrotated Hessenberg (the Arnoldi relation); run.lsq takes each column when it is final
+   std::vector<double> Hr((size_t)kdim * (kdim + 1), 0.0);
    // the delayed second pass of each column (s_j, alpha_j): the recurrence from y to Z^0's coefficients
    std::vector<std::vector<double>> spass(kdim + 1);
-   std::vector<double> alph(kdim + 1, 1.0), ccoef;
-   double* v = V;
-   c.copy(v, rhs);
-   if (cb.apply(-1.0, x, 1.0, v)) return fail();
-   double normr = c.norm(v);
-   if (normr < EPS) {
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      cleanup();
-      return 0;
-   }
-   const double tolr = atol ? tol : tol * normb;
-   rel = rel_hist(maxits + 1);
-   rel[0] = normr / normb;
+   std::vector<double> alph(kdim + 1, 1.0);
+   std::vector<double>& ccoef = run.y;
    int iter = 0, i = 0;
-   if (print_level > 0) {
-      printf("--------------------------------------------------------------------------------\n");
-      printf("Start FlexGMRES(%d)\n", kdim);
-      printf("Residual Tol: %e\nMax number of inner iterations: %d\n", tolr, maxits);
-      printf("--------------------------------------------------------------------------------\n");
-      printf("Step    Residual norm  Relative res.  Convergence Rate\n");
-      printf("%5d   %8e   %8e   N/A\n", 0, normr, rel[0]);
-   }
    double* dsc = g_k.scal;  // device scalars of step j (m = j + 1): [0, 2m) the sweep, [2m] ||u_j||^2
    std::vector<double> hh, coef;
    bool broke = false, converged = false;
-   if (2 * (kdim + 1) + 1 > KScratch::kScal) return fail();
    while (iter < maxits) {
-      rs[0] = normr;
+      run.lsq.start(normr);
       c.scale(V, nullptr, 1.0 / normr);
       i = 0;                 // final columns of H in this cycle
       double beta = 0.0;     // ||u_j|| of the provisional column j (j >= 1)
@@ -1418,15 +1553,15 @@ int fgmres_dcgs2_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int 
          if (more) {
             if (cb.prec) {
                double* zj = Z + (size_t)j * n;  // z_j^0 = M^-1 v_j^0, w = A z_j^0
-               if (cb.solve(zj, vj) || cb.apply(1.0, zj, 0.0, w)) return fail();
+               if (cb.solve(zj, vj) || cb.apply(1.0, zj, 0.0, w)) return -1;
             } else if (cb.apply(1.0, vj, 0.0, w)) {
-               return fail();
+               return -1;
             }
          }
          const int m = j + 1;
          hh.assign(2 * m + 1, 0.0);
-         if (c.dots_ab(vj, more ? w : nullptr, V, m, dsc)) return fail();
-         if (c.read(dsc, 2 * m + 1, hh.data())) return fail();  // (T is stale when !more)
+         if (c.dots_ab(vj, more ? w : nullptr, V, m, dsc)) return -1;
+         if (c.read(dsc, 2 * m + 1, hh.data())) return -1;  // (T is stale when !more)
          if (j > 0) beta = std::sqrt(hh[2 * m]);
          // the delayed second pass of column j: s = hh[0, j), omega = hh[j]
          double alpha = 1.0, ss = 0.0;
@@ -1443,29 +1578,11 @@ int fgmres_dcgs2_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int 
             // fgmres.c:160-200 on that column: the previous rotations, a new one, the residual estimate
             i = j;
             iter++;
-            double* Hc = H.data() + (size_t)(i - 1) * (kdim + 1);
-            for (int k = 0; k <= i; k++) Hc[k] = Hrc[k];
-            for (int k = 1; k < i; k++) {
-               const double hii = Hc[k - 1];
-               Hc[k - 1] = cs[k - 1] * hii + sn[k - 1] * Hc[k];
-               Hc[k] = -sn[k - 1] * hii + cs[k - 1] * Hc[k];
-            }
-            const double hii = Hc[i - 1], hii1 = Hc[i];
-            const double gam = std::sqrt(hii * hii + hii1 * hii1);
-            if (std::fabs(gam) < EPS) {
+            if (!run.push(Hrc, iter)) {
                broke = true;
                break;
             }
-            cs[i - 1] = hii / gam;
-            sn[i - 1] = hii1 / gam;
-            rs[i] = -sn[i - 1] * rs[i - 1];
-            rs[i - 1] = cs[i - 1] * rs[i - 1];
-            Hc[i - 1] = cs[i - 1] * hii + sn[i - 1] * hii1;
-            normr = std::fabs(rs[i]);
-            rel[iter] = normr / normb;
-            if (print_level > 0)
-               printf("%5d   %8e   %8e   %8.6f\n", iter, normr, rel[iter], rel[iter] / rel[iter - 1]);
-            if (normr <= tolr) {
+            if (normr <= run.tolr) {
                converged = true;
                break;
             }
@@ -1492,121 +1609,52 @@ int fgmres_dcgs2_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int 
          }
          coef[2 * j] = vjw / alpha;
          coef[2 * j + 1] = 1.0 / alpha;
-         if (c.dcgs2_update(V, w, j, coef, dsc + 2 * (m + 1))) return fail();  // ||u_{j+1}||^2 where step j + 1 reads it
+         if (c.dcgs2_update(V, w, j, coef, dsc + 2 * (m + 1))) return -1;  // ||u_{j+1}||^2 where step j + 1 reads it
       }
       if (broke) break;
-      if (print_level == 0)
-         printf("Rel. residual at the end of current cycle (# of steps per cycle/total its: %d/%d): %e \n", kdim,
-                iter, rel[iter]);
+      run.cycle_end(kdim, iter);
       if (i > 0) {
-         rs[i - 1] /= H[(size_t)(i - 1) * (kdim + 1) + i - 1];
-         for (int k = i - 2; k >= 0; k--) {
-            for (int q = k + 1; q < i; q++) rs[k] -= H[(size_t)q * (kdim + 1) + k] * rs[q];
-            rs[k] /= H[(size_t)k * (kdim + 1) + k];
-         }
-         if (!cb.prec) {
-            if (c.combine(x, V, i, rs.data())) return fail();
-         } else {
+         ccoef = run.lsq.solve(i);
+         if (cb.prec) {
             // x += sum_j y_j z_j with z_j = (z_j^0 - sum_{k<j} s_jk z_k) / alpha_j: from the last column down,
             // c_j = y_j / alpha_j moves -c_j s_jk onto z_k's coefficient
-            ccoef.assign(rs.begin(), rs.begin() + i);
             for (int q = i - 1; q >= 0; q--) {
                ccoef[q] /= alph[q];
                for (int k = 0; k < q && k < (int)spass[q].size(); k++) ccoef[k] -= ccoef[q] * spass[q][k];
             }
-            if (c.combine(x, Z, i, ccoef.data())) return fail();
          }
+         if (c.combine(x, cb.prec ? Z : V, i, ccoef.data())) return -1;
       }
-      if (converged || normr <= tolr) break;
-      // restart (fgmres.c:236-243): v = rhs - A x through w.  The reference keeps the Givens estimate as the
-      // new cycle's norm, so its first basis vector is not of unit length; MGS tolerates that, but the block
-      // orthogonalisations assume an orthonormal basis, so they restart from the true norm (one dot)
-      double* w = V + n;
-      c.copy(V, rhs);
-      if (cb.apply(1.0, x, 0.0, w)) return fail();
-      hipLaunchKernelGGL(k_sub, dim3(egrid(n)), dim3(256), 0, c.s, V, V, w, n);
+      if (converged || normr <= run.tolr) break;
+      // restart.  The reference keeps the Givens estimate as the new cycle's norm, so its first basis vector is
+      // not of unit length; MGS tolerates that, but the block orthogonalisations assume an orthonormal basis, so
+      // they restart from the true norm (one dot)
+      if (run.restart(x, rhs, V + n)) return -1;
       normr = c.norm(V);
    }
-   *prel_res = normr / normb;
-   *piter = iter;
-   *prel_res_v = rel;
-   cleanup();
-   return 0;
+   return run.done(normr / run.normb, iter);
 }
 
 // ---- FGMRES (fgmres.c:3-252) on device vectors ----------------------------------------------------
 int fgmres_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int maxits, int atol, double tol,
                double* prel_res, double** prel_res_v, int* piter, int print_level)
 {
-   const size_t n = cb.n;
-   Ctx c{current_stream(), n, cb.comm};
-   const double EPS = DBL_EPSILON;
-   if (cb.n_global == 0) {  // (a row shard may hold no rows: it still takes part in every all-reduce)
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      return 0;
-   }
-   const double normb = c.norm(rhs);
-   if (normb < EPS) {
-      NFFT4GP_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(double) * n, c.s));
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      return 0;
-   }
    const int ortho = fgmres_ortho();
-   if (ortho == 2)
-      return fgmres_dcgs2_dev(cb, x, rhs, kdim, maxits, atol, tol, prel_res, prel_res_v, piter, print_level);
+   Ctx c{current_stream(), cb.n, cb.comm};
+   FgmresRun run{cb, c, print_level, prel_res, prel_res_v, piter};
+   // the step's device scalars: i + 1 (MGS), 2 i + 4 (block CGS2), 2 (i + 1) + 1 (DCGS2) of KScratch::kScal
    const int kmax = ortho ? KScratch::kScal / 2 - 2 : KScratch::kScal - 2;
-   if (kdim > kmax) {
-      fprintf(stderr, "nfft4gp_amd: Nfft4GPSolverFgmres: restart dimension %d above %d\n", kdim, kmax);
-      return -1;
-   }
-   double *V = nullptr, *Z = nullptr;
-   // without a preconditioner z_i = v_i: the combination reads V and no Z is kept
-   if (dmalloc(&V, n * (size_t)(kdim + 1)) || (cb.prec && dmalloc(&Z, n * (size_t)(kdim + 1)))) return -1;
-   auto cleanup = [&]() {
-      (void)hipStreamSynchronize(c.s);
-      (void)hipFree(V);
-      (void)hipFree(Z);
-   };
-   double* rel = nullptr;
-   // every error exit: the bases and the history are released
-   auto fail = [&]() -> int {
-      free(rel);
-      rel = nullptr;
-      cleanup();
-      return -1;
-   };
-   std::vector<double> H((size_t)kdim * (kdim + 1), 0.0), cs(kdim), sn(kdim), rs(kdim + 1);
-   double* v = V;
-   c.copy(v, rhs);
-   if (cb.apply(-1.0, x, 1.0, v)) return fail();
-   double normr = c.norm(v);
-   if (normr < EPS) {
-      *prel_res = 0.0;
-      *piter = 0;
-      *prel_res_v = rel_hist(1);
-      cleanup();
-      return 0;
-   }
-   const double tolr = atol ? tol : tol * normb;
-   rel = rel_hist(maxits + 1);
-   rel[0] = normr / normb;
+   const int rc0 = run.begin(x, rhs, kdim, kmax, maxits, atol, tol);
+   if (rc0) return rc0 < 0 ? -1 : 0;
+   if (ortho == 2) return fgmres_dcgs2_cycles(run, x, rhs, kdim, maxits);
+   const size_t n = c.n;
+   double *V = run.V, *Z = run.Z;
+   double& normr = run.normr;
    int iter = 0, i = 0;
-   double* w = V;
-   if (print_level > 0) {
-      printf("--------------------------------------------------------------------------------\n");
-      printf("Start FlexGMRES(%d)\n", kdim);
-      printf("Residual Tol: %e\nMax number of inner iterations: %d\n", tolr, maxits);
-      printf("--------------------------------------------------------------------------------\n");
-      printf("Step    Residual norm  Relative res.  Convergence Rate\n");
-      printf("%5d   %8e   %8e   N/A\n", 0, normr, rel[0]);
-   }
+   double *v = V, *w = V;
    bool broke = false;
    while (iter < maxits) {
-      rs[0] = normr;
+      run.lsq.start(normr);
       c.scale(v, nullptr, 1.0 / normr);
       i = 0;
       while (i < kdim && iter < maxits) {
@@ -1616,9 +1664,9 @@ int fgmres_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int maxits
          w = V + (size_t)i * n;
          if (cb.prec) {
             double* z = Z + (size_t)(i - 1) * n;
-            if (cb.solve(z, v) || cb.apply(1.0, z, 0.0, w)) return fail();
+            if (cb.solve(z, v) || cb.apply(1.0, z, 0.0, w)) return -1;
          } else {
-            if (cb.apply(1.0, v, 0.0, w)) return fail();
+            if (cb.apply(1.0, v, 0.0, w)) return -1;
          }
          double* hd = g_k.scal;
          std::vector<double> hcol(i + 1);
@@ -1626,25 +1674,15 @@ int fgmres_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int maxits
             // Nfft4GPModifiedGS (matops.c:274-346) with k = i-1, no re-orthogonalisation: one launch for the
             // sweep where the grid fits (k_mgs_chain), else one per projection
             const int rc = c.mgs_chain(w, V, i, hd);
-            if (rc < 0) return fail();
-            if (rc > 0) {
-               // the per-projection chain, on the grid of the one-launch form this n would take (bitwise equal)
-               unsigned mg = 0;
-               if (c.mgs_form(&mg) < 0) mg = 0;
-               for (int j = 0; j < i; j++)
-                  if (c.gs(w, j ? V + (size_t)(j - 1) * n : nullptr, j ? hd + j - 1 : nullptr, V + (size_t)j * n,
-                           hd + j, mg))
-                     return fail();
-               if (c.gs(w, V + (size_t)(i - 1) * n, hd + i - 1, nullptr, hd + i, mg)) return fail();
-            }
-            if (c.read(hd, i + 1, hcol.data())) return fail();
-            if (rc == 0 && c.chain_failed()) return fail();
+            if (rc < 0 || (rc > 0 && c.gs_chain(w, V, i, hd))) return -1;
+            if (c.read(hd, i + 1, hcol.data())) return -1;
+            if (rc == 0 && c.chain_failed()) return -1;
          } else {
             // classical passes h = V^T w, w -= V h; a second one only when the first dropped ||w|| below 0.7071
             // of its value before it (the DGKS test of the reference's MGS2, matops.c:348-440); H(:, i) = the
             // sum of the passes' projections, ||w|| after the last
             std::vector<double> hh(2 * i + 4);
-            if (c.block_cgs2(w, V, i, hd) || c.read(hd, 2 * i + 4, hh.data())) return fail();
+            if (c.block_cgs2(w, V, i, hd) || c.read(hd, 2 * i + 4, hh.data())) return -1;
             for (int j = 0; j < i; j++) hcol[j] = hh[j];
             hcol[i] = hh[i];
             if (hh[2 * i + 3] != 0.0) {
@@ -1654,55 +1692,25 @@ int fgmres_dev(Callbacks& cb, double* x, const double* rhs, int kdim, int maxits
             }
          }
          const double t = std::sqrt(hcol[i]);
-         double* Hc = H.data() + (size_t)(i - 1) * (kdim + 1);
-         for (int j = 0; j < i; j++) Hc[j] = hcol[j];
-         Hc[i] = t;
+         hcol[i] = t;
          c.scale(w, nullptr, 1.0 / t);
-         for (int j = 1; j < i; j++) {
-            const double hii = Hc[j - 1];
-            Hc[j - 1] = cs[j - 1] * hii + sn[j - 1] * Hc[j];
-            Hc[j] = -sn[j - 1] * hii + cs[j - 1] * Hc[j];
-         }
-         const double hii = Hc[i - 1], hii1 = Hc[i];
-         const double gam = std::sqrt(hii * hii + hii1 * hii1);
-         if (std::fabs(gam) < EPS) {
+         if (!run.push(hcol.data(), iter)) {
             broke = true;  // fgmres.c:179-182: leave without updating x
             break;
          }
-         cs[i - 1] = hii / gam;
-         sn[i - 1] = hii1 / gam;
-         rs[i] = -sn[i - 1] * rs[i - 1];
-         rs[i - 1] = cs[i - 1] * rs[i - 1];
-         Hc[i - 1] = cs[i - 1] * hii + sn[i - 1] * hii1;
-         normr = std::fabs(rs[i]);
-         rel[iter] = normr / normb;
-         if (print_level > 0)
-            printf("%5d   %8e   %8e   %8.6f\n", iter, normr, rel[iter], rel[iter] / rel[iter - 1]);
-         if (normr <= tolr) break;
+         if (normr <= run.tolr) break;
       }
       if (broke) break;
-      if (print_level == 0)
-         printf("Rel. residual at the end of current cycle (# of steps per cycle/total its: %d/%d): %e \n", kdim,
-                iter, rel[iter]);
-      rs[i - 1] /= H[(size_t)(i - 1) * (kdim + 1) + i - 1];
-      for (int k = i - 2; k >= 0; k--) {
-         for (int j = k + 1; j < i; j++) rs[k] -= H[(size_t)j * (kdim + 1) + k] * rs[j];
-         rs[k] /= H[(size_t)k * (kdim + 1) + k];
-      }
-      if (c.combine(x, cb.prec ? Z : V, i, rs.data())) return fail();
-      if (normr <= tolr) break;
-      // restart (fgmres.c:236-243): v = rhs - A x through w; normr keeps the Givens estimate
+      run.cycle_end(kdim, iter);
+      run.y = run.lsq.solve(i);
+      if (c.combine(x, cb.prec ? Z : V, i, run.y.data())) return -1;
+      if (normr <= run.tolr) break;
+      // restart; normr keeps the Givens estimate
       v = V;
-      c.copy(v, rhs);
-      if (cb.apply(1.0, x, 0.0, w)) return fail();
-      hipLaunchKernelGGL(k_sub, dim3(egrid(n)), dim3(256), 0, c.s, v, v, w, n);
-      if (ortho) normr = c.norm(v);  // block CGS2: restart from the true norm (see fgmres_dcgs2_dev)
+      if (run.restart(x, rhs, w)) return -1;
+      if (ortho) normr = c.norm(v);  // block CGS2: restart from the true norm (see fgmres_dcgs2_cycles)
    }
-   *prel_res = normr / normb;
-   *piter = iter;
-   *prel_res_v = rel;
-   cleanup();
-   return 0;
+   return run.done(normr / run.normb, iter);
 }
 
 // ---- FGMRES on a batch of right-hand sides (the predict's std solves) ---------------------------------------
@@ -1733,86 +1741,45 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
    if (m <= 0) return 0;
    if (cb.comm || cb.n_global != cb.n) return -1;
    const bool multi = cb.mv_dev && cb.matvec == (func_symmatvec)&Nfft4GPAdditiveNFFTMatSymv;
-   const unsigned ggrid = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 4095) / 4096, kKMaxBlocks));
+   const unsigned ggrid = gs_grid(n);
    // device scratch: partials / tickets per slot, the step's scalars [j][s], factors, the running list
-   double *part = nullptr, *hd = nullptr, *dfac = nullptr, *dcoef = nullptr;
-   const double** dcols = nullptr;
-   unsigned int* ticket = nullptr;
-   int* dact = nullptr;
-   double* pin = nullptr;  // pinned: [0, m) factors, then the combine's coefficients and column pointers
-   int* pact = nullptr;    // pinned: the running list
+   DevBuf<double> part, hd, dfac, dcoef;
+   DevBuf<const double*> dcols;
+   DevBuf<unsigned int> ticket;
+   DevBuf<int> dact;
+   PinBuf<double> pin;  // pinned: [0, m) factors, then the combine's coefficients and column pointers
+   PinBuf<int> pact;    // pinned: the running list
    // the one-launch MGS sweep (k_mgs_chain<.., true>): device column table, error word
-   const double** dvcols = nullptr;
-   const double** pvcols = nullptr;  // pinned staging of new column pointers
-   int *derr = nullptr, *herr = nullptr;
+   DevBuf<const double*> dvcols;
+   PinBuf<const double*> pvcols;  // pinned staging of new column pointers
+   DevBuf<int> derr;
+   PinBuf<int> herr;
    int vcols_up = 0;
-   hipEvent_t pin_ev = nullptr;  // the last copy out of pin / pact
-   std::vector<double*> groups;  // basis column groups (V, then Z when preconditioned)
-   std::vector<double*> Vc, Zc;  // column j of every system: Vc[j] + s n
-   int hcap = 0;                 // columns of hd
-   auto cleanup = [&]() {
-      (void)hipStreamSynchronize(st);
-      for (double* g : groups) (void)hipFree(g);
-      (void)hipFree(part);
-      (void)hipFree(hd);
-      (void)hipFree(dfac);
-      (void)hipFree(dcoef);
-      (void)hipFree(dcols);
-      (void)hipFree(ticket);
-      (void)hipFree(dact);
-      if (pin) (void)hipHostFree(pin);
-      if (pact) (void)hipHostFree(pact);
-      (void)hipFree(dvcols);
-      (void)hipFree(derr);
-      if (pvcols) (void)hipHostFree(pvcols);
-      if (herr) (void)hipHostFree(herr);
-      if (pin_ev) (void)hipEventDestroy(pin_ev);
-   };
-   auto fail = [&]() -> int {
-      cleanup();
-      return -1;
-   };
+   EventHold pin_ev;                    // the last copy out of pin / pact
+   std::vector<DevBuf<double>> groups;  // basis column groups (V, then Z when preconditioned)
+   std::vector<double*> Vc, Zc;         // column j of every system: Vc[j] + s n
+   int hcap = 0;                        // columns of hd
+   SyncOnExit sync{st};                 // (declared after every buffer: the stream drains before they are freed)
    const int kcyc = std::min(kdim, maxits) + 1;  // columns a cycle can combine
    const int kpin = 4 * m + 2 * kcyc + 16;
-   if (dmalloc(&part, (size_t)m * kKMaxBlocks) || dmalloc(&ticket, (size_t)m * kTicketWords) || dmalloc(&dfac, m) ||
-       dmalloc(&dact, m) || dmalloc(&dcoef, (size_t)kcyc) || dmalloc(&dcols, (size_t)kcyc))
-      return fail();
-   if (hipHostMalloc((void**)&pin, sizeof(double) * kpin) != hipSuccess) {
-      pin = nullptr;
-      return fail();
-   }
-   if (hipHostMalloc((void**)&pact, sizeof(int) * m) != hipSuccess) {
-      pact = nullptr;
-      return fail();
-   }
+   if (part.alloc((size_t)m * kKMaxBlocks) || ticket.alloc((size_t)m * kTicketWords) || dfac.alloc(m) ||
+       dact.alloc(m) || dcoef.alloc((size_t)kcyc) || dcols.alloc((size_t)kcyc) || pin.alloc(kpin) || pact.alloc(m))
+      return -1;
    const int colcap = std::min(kdim, maxits) + 2;
-   if (dmalloc(&dvcols, (size_t)colcap) || dmalloc(&derr, 1)) return fail();
-   if (hipHostMalloc((void**)&pvcols, sizeof(double*) * 64) != hipSuccess ||
-       hipHostMalloc((void**)&herr, sizeof(int)) != hipSuccess) {
-      pvcols = nullptr;
-      herr = nullptr;
-      return fail();
-   }
+   if (dvcols.alloc((size_t)colcap) || derr.alloc(1) || pvcols.alloc(64) || herr.alloc(1)) return -1;
    *herr = 0;
    NFFT4GP_HIP_CHECK(hipMemsetAsync(derr, 0, sizeof(int), st));
-   static int occ_batch = -1;  // resident k_mgs_chain<1024, 4, true> workgroups on the device
-   if (occ_batch < 0) {
-      int dev = 0, occ = 0;
-      hipDeviceProp_t prop;
-      occ_batch = 0;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_mgs_chain<1024, 4, true>, 1024, 0) == hipSuccess)
-         occ_batch = occ * prop.multiProcessorCount;
-   }
-   NFFT4GP_HIP_CHECK(hipEventCreateWithFlags(&pin_ev, hipEventDisableTiming));
-   NFFT4GP_HIP_CHECK(hipEventRecord(pin_ev, st));
+   // resident k_mgs_chain<1024, 4, true> workgroups on the device
+   static const int occ_batch = resident_workgroups(k_mgs_chain<1024, 4, true>);
+   NFFT4GP_HIP_CHECK(hipEventCreateWithFlags(&pin_ev.e, hipEventDisableTiming));
+   NFFT4GP_HIP_CHECK(hipEventRecord(pin_ev.e, st));
    // the staging buffers are rewritten only after the copies out of them have run
    auto pin_wait = [&]() -> int {
-      NFFT4GP_HIP_CHECK(hipEventSynchronize(pin_ev));
+      NFFT4GP_HIP_CHECK(hipEventSynchronize(pin_ev.e));
       return 0;
    };
    auto pin_done = [&]() -> int {
-      NFFT4GP_HIP_CHECK(hipEventRecord(pin_ev, st));
+      NFFT4GP_HIP_CHECK(hipEventRecord(pin_ev.e, st));
       return 0;
    };
    NFFT4GP_HIP_CHECK(hipMemsetAsync(ticket, 0, sizeof(unsigned int) * (size_t)m * kTicketWords, st));
@@ -1822,13 +1789,13 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
       while ((int)Vc.size() < need) {
          const int g = std::min(kG, std::max(1, need + kG - 1 - (int)Vc.size()));
          for (int pass = 0; pass < (cb.prec ? 2 : 1); pass++) {
-            double* base = nullptr;
-            if (hipMalloc((void**)&base, sizeof(double) * n * m * g) != hipSuccess) {
+            groups.emplace_back();
+            if (groups.back().alloc(n * m * g)) {
                fprintf(stderr, "nfft4gp_amd: FGMRES batch of %d: no memory for %zu basis columns of %zu\n", m,
                        Vc.size() + g, n);
                return -1;
             }
-            groups.push_back(base);
+            double* base = groups.back();
             for (int k = 0; k < g; k++) (pass ? Zc : Vc).push_back(base + (size_t)k * n * m);
          }
       }
@@ -1837,11 +1804,10 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
    auto ensure_h = [&](int cols) -> int {
       if (cols <= hcap) return 0;
       const int nc = std::max(cols, 2 * hcap);
-      double* nh = nullptr;
-      if (dmalloc(&nh, (size_t)nc * m)) return -1;
+      DevBuf<double> nh;
+      if (nh.alloc((size_t)nc * m)) return -1;
       NFFT4GP_HIP_CHECK(hipStreamSynchronize(st));
-      (void)hipFree(hd);
-      hd = nh;
+      std::swap(hd.p, nh.p);  // (nh frees the old columns)
       hcap = nc;
       return 0;
    };
@@ -1901,32 +1867,22 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
       NFFT4GP_HIP_CHECK(hipGetLastError());
       return 0;
    };
-   if (2 * kcyc + 2 * m > kpin) return fail();
+   if (2 * kcyc + 2 * m > kpin) return -1;
 
    struct Sys {
       double normb = 0, normr = 0, tolr = 0, rel_prev = 0;
-      std::vector<std::vector<double>> H;  // H[i - 1]: column i - 1 (i + 1 entries)
-      std::vector<double> cs, sn, rs;
-      std::string log;
-      bool done = false;
+      GivensLsq lsq;
+      std::string log;  // its report lines
    };
    std::vector<Sys> S(m);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wformat-security"
-   auto logf = [&](int s, const char* fmt, auto... a) {  // (fmt: the literals below)
-      char buf[256];
-      snprintf(buf, sizeof(buf), fmt, a...);
-      S[s].log += buf;
-   };
-#pragma clang diagnostic pop
    for (int s = 0; s < m; s++) NFFT4GP_HIP_CHECK(hipMemsetAsync(X + (size_t)s * ldx, 0, sizeof(double) * n, st));
-   if (ensure_cols(2) || ensure_h(2)) return fail();
+   if (ensure_cols(2) || ensure_h(2)) return -1;
    act.resize(m);
    for (int s = 0; s < m; s++) act[s] = s;
-   if (upload_act()) return fail();
+   if (upload_act()) return -1;
    // ||b_s|| (c.norm: the dot of b with itself), then v_0 = b - A 0 = b
    std::vector<double> hh;
-   if (gs(const_cast<double*>(B), ldb, nullptr, 0, nullptr, B, ldb, hd) || read(hd, m, hh)) return fail();
+   if (gs(const_cast<double*>(B), ldb, nullptr, 0, nullptr, B, ldb, hd) || read(hd, m, hh)) return -1;
    for (int s = 0; s < m; s++) {
       S[s].normb = std::sqrt(hh[s]);
       S[s].normr = S[s].normb;  // ||v_0|| = ||b||: the same vector
@@ -1936,65 +1892,45 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
    act.clear();
    for (int s = 0; s < m; s++) {
       Sys& y = S[s];
-      if (y.normb < EPS) {  // x = 0 (set above), rel_res 0, 0 iterations
-         y.done = true;
-         continue;
-      }
+      if (y.normb < EPS) continue;  // x = 0 (set above), rel_res 0, 0 iterations
       y.tolr = atol ? tol : tol * y.normb;
       y.rel_prev = y.normr / y.normb;
-      if (print_level > 0) {
-         logf(s, "--------------------------------------------------------------------------------\n");
-         logf(s, "Start FlexGMRES(%d)\n", kdim);
-         logf(s, "Residual Tol: %e\nMax number of inner iterations: %d\n", y.tolr, maxits);
-         logf(s, "--------------------------------------------------------------------------------\n");
-         logf(s, "Step    Residual norm  Relative res.  Convergence Rate\n");
-         logf(s, "%5d   %8e   %8e   N/A\n", 0, y.normr, y.rel_prev);
-      }
+      if (print_level > 0) Report{&y.log}.header("FlexGMRES", kdim, y.tolr, maxits, y.normr, y.rel_prev);
       act.push_back(s);
    }
-   if (upload_act()) return fail();
-   // the end of a cycle of system s after i steps (fgmres.c:221-235): back substitution, x += Z y
-   auto finish_cycle = [&](int s, int i) -> int {
-      Sys& y = S[s];
-      if (i <= 0) return 0;
-      std::vector<double>& rs = y.rs;
-      rs[i - 1] /= y.H[i - 1][i - 1];
-      for (int k = i - 2; k >= 0; k--) {
-         for (int j = k + 1; j < i; j++) rs[k] -= y.H[j][k] * rs[j];
-         rs[k] /= y.H[k][k];
-      }
-      return combine(s, cb.prec ? Zc : Vc, i, rs.data());
-   };
+   if (upload_act()) return -1;
    int iter = 0;
+   // the end of a cycle of system s after i steps (fgmres.c:212-235): its line, back substitution, x += Z y
+   auto finish_cycle = [&](int s, int i) -> int {
+      if (print_level == 0) Report{&S[s].log}.cycle_end(kdim, iter, S[s].rel_prev);
+      return combine(s, cb.prec ? Zc : Vc, i, S[s].lsq.solve(i).data());
+   };
    std::vector<double> fac(m, 0.0);
    while (!act.empty() && iter < maxits) {
       for (int s : act) {
-         S[s].rs.assign(1, S[s].normr);
-         S[s].H.clear();
-         S[s].cs.clear();
-         S[s].sn.clear();
+         S[s].lsq.start(S[s].normr);
          fac[s] = 1.0 / S[s].normr;
       }
-      if (scale(Vc[0], fac)) return fail();
+      if (scale(Vc[0], fac)) return -1;
       int i = 0;
       while (!act.empty() && i < kdim && iter < maxits) {
          i++;
          iter++;
-         if (ensure_cols(i + 1) || ensure_h(i + 1)) return fail();
+         if (ensure_cols(i + 1) || ensure_h(i + 1)) return -1;
          std::vector<const double*> xs;
          std::vector<double*> ys;
          for (int s : act) {
             double* v = Vc[i - 1] + (size_t)s * n;
             if (cb.prec) {
                double* z = Zc[i - 1] + (size_t)s * n;
-               if (cb.solve(z, v)) return fail();
+               if (cb.solve(z, v)) return -1;
                xs.push_back(z);
             } else {
                xs.push_back(v);
             }
             ys.push_back(Vc[i] + (size_t)s * n);
          }
-         if (apply(xs, ys)) return fail();
+         if (apply(xs, ys)) return -1;
          // Nfft4GPModifiedGS (matops.c:274-346) with k = i - 1: the whole sweep of every running system in one
          // launch where the grid fits (k_mgs_chain), else one launch per projection for all of them
          const char* ce = getenv("NFFT4GP_AMD_MGS_CHAIN");
@@ -2002,12 +1938,12 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
                             (long)ggrid * (long)act.size() <= (long)occ_batch && i + 1 <= colcap && !*herr;
          if (chain) {
             while (vcols_up <= i) {  // the column table: pointers of columns not uploaded yet
-               if (pin_wait()) return fail();
+               if (pin_wait()) return -1;
                const int cnt = std::min(64, i + 1 - vcols_up);
                for (int k = 0; k < cnt; k++) pvcols[k] = Vc[vcols_up + k];
                NFFT4GP_HIP_CHECK(hipMemcpyAsync(dvcols + vcols_up, pvcols, sizeof(double*) * cnt,
                                                 hipMemcpyHostToDevice, st));
-               if (pin_done()) return fail();
+               if (pin_done()) return -1;
                vcols_up += cnt;
             }
             NFFT4GP_HIP_CHECK(hipMemsetAsync(hd, 0xFF, sizeof(double) * (size_t)(i + 1) * m, st));  // kChainUnset
@@ -2020,13 +1956,13 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
             for (int j = 0; j < i; j++)
                if (gs(Vc[i], n, j ? Vc[j - 1] : nullptr, n, j ? hd + (size_t)(j - 1) * m : nullptr, Vc[j], n,
                       hd + (size_t)j * m))
-                  return fail();
-            if (gs(Vc[i], n, Vc[i - 1], n, hd + (size_t)(i - 1) * m, nullptr, 0, hd + (size_t)i * m)) return fail();
+                  return -1;
+            if (gs(Vc[i], n, Vc[i - 1], n, hd + (size_t)(i - 1) * m, nullptr, 0, hd + (size_t)i * m)) return -1;
          }
-         if (read(hd, (size_t)(i + 1) * m, hh)) return fail();
+         if (read(hd, (size_t)(i + 1) * m, hh)) return -1;
          if (chain && *herr) {
             fprintf(stderr, "nfft4gp_amd: FGMRES batch: the one-launch MGS sweep's wait gave up\n");
-            return fail();
+            return -1;
          }
          std::vector<int> keep, conv;
          for (int s : act) {
@@ -2036,54 +1972,31 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
             for (int j = 0; j < i; j++) Hc[j] = hh[(size_t)j * m + s];
             Hc[i] = t;
             fac[s] = 1.0 / t;
-            for (int j = 1; j < i; j++) {
-               const double hii = Hc[j - 1];
-               Hc[j - 1] = y.cs[j - 1] * hii + y.sn[j - 1] * Hc[j];
-               Hc[j] = -y.sn[j - 1] * hii + y.cs[j - 1] * Hc[j];
-            }
-            const double hii = Hc[i - 1], hii1 = Hc[i];
-            const double gam = std::sqrt(hii * hii + hii1 * hii1);
-            if (std::fabs(gam) < EPS) {  // fgmres.c:179-182: leave without updating x
-               y.done = true;
+            if (!y.lsq.push(Hc.data(), &y.normr)) {  // fgmres.c:179-182: leave without updating x
                res.iters[s] = iter;
                res.rel_res[s] = y.normr / y.normb;
                continue;
             }
-            y.cs.push_back(hii / gam);
-            y.sn.push_back(hii1 / gam);
-            y.rs.push_back(-y.sn[i - 1] * y.rs[i - 1]);
-            y.rs[i - 1] = y.cs[i - 1] * y.rs[i - 1];
-            Hc[i - 1] = y.cs[i - 1] * hii + y.sn[i - 1] * hii1;
-            y.H.push_back(std::move(Hc));
-            y.normr = std::fabs(y.rs[i]);
             const double rel = y.normr / y.normb;
-            if (print_level > 0) logf(s, "%5d   %8e   %8e   %8.6f\n", iter, y.normr, rel, rel / y.rel_prev);
+            if (print_level > 0) Report{&y.log}.step(iter, y.normr, rel, y.rel_prev);
             y.rel_prev = rel;
             (y.normr <= y.tolr ? conv : keep).push_back(s);
          }
-         if (scale(Vc[i], fac)) return fail();
-         for (int s : conv) {  // converged in this cycle: its end (fgmres.c:212-235)
-            if (print_level == 0)
-               logf(s, "Rel. residual at the end of current cycle (# of steps per cycle/total its: %d/%d): %e \n", kdim,
-                    iter, S[s].rel_prev);
-            if (finish_cycle(s, i)) return fail();
-            S[s].done = true;
+         if (scale(Vc[i], fac)) return -1;
+         for (int s : conv) {  // converged in this cycle: its end
+            if (finish_cycle(s, i)) return -1;
             res.iters[s] = iter;
             res.rel_res[s] = S[s].normr / S[s].normb;
          }
          if (keep.size() != act.size()) {
             act = keep;
-            if (!act.empty() && upload_act()) return fail();
+            if (!act.empty() && upload_act()) return -1;
          }
       }
       if (act.empty()) break;
       // the cycle ends for every running system together (restart dimension or maxits reached)
-      for (int s : act) {
-         if (print_level == 0)
-            logf(s, "Rel. residual at the end of current cycle (# of steps per cycle/total its: %d/%d): %e \n", kdim,
-                 iter, S[s].rel_prev);
-         if (finish_cycle(s, i)) return fail();
-      }
+      for (int s : act)
+         if (finish_cycle(s, i)) return -1;
       if (iter >= maxits) break;
       // restart (fgmres.c:236-243): v = b - A x; normr keeps the Givens estimate
       std::vector<const double*> xs;
@@ -2092,7 +2005,7 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
          xs.push_back(X + (size_t)s * ldx);
          ys.push_back(Vc[1] + (size_t)s * n);
       }
-      if (apply(xs, ys)) return fail();
+      if (apply(xs, ys)) return -1;
       for (int s : act)
          hipLaunchKernelGGL(k_sub, dim3(egrid(n)), dim3(256), 0, st, Vc[0] + (size_t)s * n, B + (size_t)s * ldb,
                             (const double*)(Vc[1] + (size_t)s * n), n);
@@ -2109,7 +2022,6 @@ int fgmres_batch_dev(Callbacks& cb, int m, double* X, size_t ldx, const double* 
          printed = true;
       }
    if (printed) fflush(stdout);
-   cleanup();
    return 0;
 }
 
@@ -2246,14 +2158,7 @@ struct LanczosRun {
       tolr = atol ? tol / beta : tol;
       rel = rel_hist(maxits + 1);
       rel[0] = normr / normb;
-      if (print_level > 0) {
-         printf("--------------------------------------------------------------------------------\n");
-         printf("Start Lanczos(%d)\n", maxits);
-         printf("Residual Tol: %e\nMax number of inner iterations: %d\n", tolr, maxits);
-         printf("--------------------------------------------------------------------------------\n");
-         printf("Step    Residual norm  Relative res.  Convergence Rate\n");
-         printf("%5d   %8e   %8e   N/A\n", 0, normr, rel[0]);
-      }
+      if (print_level > 0) Report{}.header("Lanczos", maxits, tolr, maxits, normr, rel[0]);
       c.scale(v, alias ? nullptr : z, 1.0 / beta);
       return 0;
    }
@@ -2382,8 +2287,7 @@ struct LanczosRun {
          }
          chol_size++;
          rel[iter] = normr / normb;
-         if (print_level > 0)
-            printf("%5d   %8e   %8e   %8.6f\n", iter, normr, rel[iter], rel[iter] / rel[iter - 1]);
+         if (print_level > 0) Report{}.step(iter, normr, rel[iter], rel[iter - 1]);
          if (normr <= tolr) return 1;
       } else if (print_level > 0) {
          printf("%5d   Building T\n", iter);
@@ -2724,7 +2628,6 @@ extern "C" int Nfft4GPAmdDebugOrthoSweep(int kind, double* w, const double* V, c
       return -1;
    Ctx c{current_stream(), (size_t)n, nullptr};
    double* hd = g_k.scal;
-   const size_t nn = (size_t)n;
    for (int q = 0; q < 6; q++) info[q] = 0;
    int count = 0;
    bool one_launch = false;
@@ -2740,11 +2643,7 @@ extern "C" int Nfft4GPAmdDebugOrthoSweep(int kind, double* w, const double* V, c
          one_launch = true;
       } else {
          info[0] = -1;
-         if (form < 0) mg = 0;
-         for (int j = 0; j < m; j++)
-            if (c.gs(w, j ? V + (size_t)(j - 1) * nn : nullptr, j ? hd + j - 1 : nullptr, V + (size_t)j * nn, hd + j, mg))
-               return -1;
-         if (c.gs(w, m ? V + (size_t)(m - 1) * nn : nullptr, m ? hd + m - 1 : nullptr, nullptr, hd + m, mg)) return -1;
+         if (c.gs_chain(w, V, m, hd)) return -1;
       }
    } else if (kind == 2) {
       info[2] = c.bd_vec(w, V, Z) ? 1 : 0;
@@ -2799,6 +2698,37 @@ extern "C" int Nfft4GPAmdDebugBlockGs(double* w, const double* V, const double* 
    (void)hipEventDestroy(e1);
    if (rc == 0 && h_out) rc = c.read(g_k.scal, m + 2, h_out);
    return rc;
+}
+
+// FGMRES's least-squares recurrence (GivensLsq, fgmres_lsq.hpp) on the host, for tests/test_fgmres_lsq_host.py: a
+// cycle that starts from beta and takes the k columns of the column-major (k + 1) x k upper Hessenberg H in order.
+// res[j]: the residual estimate after column j; y[0..k): the back-substituted solution; *breakdown: the column at
+// which breakdown was reported (the cycle stops there: y holds the solution of the columns before it, the rest of
+// res and y is 0), or -1.  k0 > 0: the same object first runs a cycle on (k0, beta0, H0), as before a restart.
+extern "C" int Nfft4GPAmdDebugGivensLsq(int k, double beta, const double* H, int k0, double beta0, const double* H0,
+                                        double* res, double* y, int* breakdown)
+{
+   if (k < 1 || !H || k0 < 0 || (k0 > 0 && !H0) || !res || !y || !breakdown) return -1;
+   GivensLsq lsq;
+   double normr = 0.0;
+   if (k0 > 0) {
+      lsq.start(beta0);
+      for (int j = 0; j < k0; j++)
+         if (!lsq.push(H0 + (size_t)j * (k0 + 1), &normr)) break;
+   }
+   lsq.start(beta);
+   std::fill(res, res + k, 0.0);
+   std::fill(y, y + k, 0.0);
+   *breakdown = -1;
+   for (int j = 0; j < k && *breakdown < 0; j++) {
+      if (lsq.push(H + (size_t)j * (k + 1), &normr))
+         res[j] = normr;
+      else
+         *breakdown = j;
+   }
+   const std::vector<double> sol = lsq.solve(lsq.cols());
+   std::copy(sol.begin(), sol.end(), y);
+   return 0;
 }
 
 extern "C" {
@@ -3148,8 +3078,7 @@ int Nfft4GPAdditiveNFFTGpPredict(double* x, double* data, double* label, int n, 
          BatchOut bo;
          if ((rc = fgmres_batch_dev(cb11, mb, Xs, (size_t)n, Y, (size_t)na, n, n, atol, tol, print_level, bo))) break;
          // (K12(:, i), x_i) per point: k_gs_step's dot, batched
-         const unsigned gg = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)n + 4095) / 4096, kKMaxBlocks));
-         hipLaunchKernelGGL((k_gs_batch<1024, 4>), dim3(gg, (unsigned)mb), dim3(1024), 0, s, Y, (size_t)na,
+         hipLaunchKernelGGL((k_gs_batch<1024, 4>), dim3(gs_grid((size_t)n), (unsigned)mb), dim3(1024), 0, s, Y, (size_t)na,
                             (const double*)nullptr, (size_t)0, (const double*)nullptr, (const double*)Xs, (size_t)n,
                             (size_t)n, (const int*)dall, gpart, gtick, dsc + bm);
          NFFT4GP_HIP_CHECK(hipGetLastError());

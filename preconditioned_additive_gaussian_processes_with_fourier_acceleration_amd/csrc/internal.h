@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <memory>
 #include <utility>
 #include <string>
@@ -427,6 +428,25 @@ int fsai_kernel_csr(const double* dX, int n, int ldim, int d, int lfil, const Ke
 void* fsai_create_from_device(int n, int* dia, int* dja, double* daa, const std::vector<int>& hia, hipStream_t s);
 // the number of non-finite values among count doubles (device)
 long long count_nonfinite(const double* d, size_t count, hipStream_t s);
+constexpr int kFsaiMaxK = 64;   // entries per row (lfil) the FSAI's per-row kernels hold in LDS
+constexpr int kMaxDims = 256;   // features of the FSAI's `data`
+// a device array of count T (at least one), filled from h when given; 0 or -1
+template <class T>
+int upload(T** d, const T* h, size_t count)
+{
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)d, sizeof(T) * (count ? count : 1)));
+   if (count && h) NFFT4GP_HIP_CHECK(hipMemcpy(*d, h, sizeof(T) * count, hipMemcpyHostToDevice));
+   return 0;
+}
+// The FSAI pattern's KNN rows (knn_pattern.hip): for each row i of lfil .. n-1, or of the ascending device list
+// d_rows (nrows_list of them, each >= lfil), ja[ia[i] .. ia[i] + lfil - 1] = the lfil - 1 nearest of points
+// 0 .. i-1 by (squared distance, index), then i.  variant: 4 the tile screen first, 3 the 32-row screen first,
+// 0 the fp64 bounded scan first, 2 the radix select alone, negative the default (NFFT4GP_AMD_KNN, else 4);
+// every variant gives the same rows.  Returns the number of rows that the first screening stage to run (tile,
+// 32-row or bounded) did not settle -- every row where none ran and the radix select took them all -- or -1 on
+// an error or an unknown variant.
+int knn_pattern(const double* dX, int n, int ldim, int d, int lfil, const int* dia, int* dja, hipStream_t s,
+                int variant, const int* d_rows = nullptr, int nrows_list = 0);
 // a row shard's rows of the FSAI (fsai_setup.hip): the pattern of the listed rows (ascending) -- KNN over their
 // earlier points only -- and the values of a range of pattern rows, W's column of each entry from dwcol
 int fsai_pattern_rows(const double* dX, int n, int ldim, int d, int lfil, const std::vector<int>& rows,

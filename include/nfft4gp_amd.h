@@ -960,6 +960,30 @@ int Nfft4GPAmdFeatureGpMoments(void *fgp, NFFT4GP_DOUBLE *G, NFFT4GP_DOUBLE *b, 
 int Nfft4GPAmdFeatureGpInfo(void *fgp, int *n, int *nw, int *R, int *kernel);
 /* the last evaluation's sign of det B (+1 / -1; 0: none yet, or it failed) and log|det B| */
 int Nfft4GPAmdFeatureGpStatus(void *fgp, int *det_sign, NFFT4GP_DOUBLE *logabsdet);
+/* ---- leave-one-out cross-validation of the same operator ----------------------------------------
+ * With m_i = [M^{-1}]_ii and a_i = [M^{-1} y]_i, M = Z W Z^T + mu I, training point i's prediction from the other
+ * n - 1 points has mean y_i - a_i / m_i and variance f^2 / m_i (of y: the noise is included).  Both are quadratic
+ * and linear forms of the point's features with R x R matrices, so one pass over the points gives them all.
+ * Nfft4GPAmdFeatureGpLooBind: the object does not hold X, so the data of the create call is bound once: n, d the
+ * object's, X column-major with ldim >= n.  Device pointers are borrowed (the caller keeps them alive until the next
+ * bind, unbind or free); host arrays are copied to buffers the object owns.  X == NULL unbinds and frees them. */
+int Nfft4GPAmdFeatureGpLooBind(void *fgp, const NFFT4GP_DOUBLE *X, int n, int ldim, int d, const NFFT4GP_DOUBLE *y);
+/* a func_loss like Nfft4GPAmdFeatureGpLoss (x before the transform; the transform and mask of SetOptions):
+ * *lossp = 1/(2n) sum_i [ log(f^2 / |m_i|) + a_i^2 / (f^2 m_i) + log 2 pi ], the negative mean leave-one-out log
+ * predictive density, and dloss[3] its gradient in x.  Nfft4GPOptimizationAdamSetProblem(adam,
+ * &Nfft4GPAmdFeatureGpLooLoss, fgp, 3) trains on it.  The operator is not always definite, so m_i can be <= 0: the
+ * loss uses log|m_i| and the signed m_i elsewhere, and Nfft4GPAmdFeatureGpLooStatus reports how many such points
+ * there were.  Deterministic: no atomics, the same bits from host and device data.  -1 (message) when nothing is
+ * bound, a bound row lies outside the domain, or on any condition under which Nfft4GPAmdFeatureGpLoss fails. */
+int Nfft4GPAmdFeatureGpLooLoss(void *fgp, NFFT4GP_DOUBLE *x, NFFT4GP_DOUBLE *lossp, NFFT4GP_DOUBLE *dloss);
+/* the per-point leave-one-out mean and variance (n each, host or device; either may be NULL) at the transformed
+ * hyperparameters; a point with m_i <= 0 has a negative variance, returned as it comes out.  *n_nonpositive (may be
+ * NULL): the number of such points. */
+int Nfft4GPAmdFeatureGpLooPredict(void *fgp, NFFT4GP_DOUBLE f, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE mu,
+                                  NFFT4GP_DOUBLE *mean, NFFT4GP_DOUBLE *var, long long *n_nonpositive);
+/* the number of points with m_i <= 0 at the last leave-one-out evaluation */
+int Nfft4GPAmdFeatureGpLooStatus(void *fgp, long long *n_nonpositive);
+/* releases the object and what Nfft4GPAmdFeatureGpLooBind copied */
 void Nfft4GPAmdFeatureGpFree(void *fgp);
 
 /* ---- host-only helpers (no GPU needed): the setup math of the device plan, exported so the CPU

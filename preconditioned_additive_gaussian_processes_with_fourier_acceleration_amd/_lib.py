@@ -292,6 +292,11 @@ _SIGS = {
     "Nfft4GPAmdFeatureGpMoments": (C.c_int, [vp, vp, vp, dp]),
     "Nfft4GPAmdFeatureGpInfo": (C.c_int, [vp, ip, ip, ip, ip]),
     "Nfft4GPAmdFeatureGpStatus": (C.c_int, [vp, ip, dp]),
+    "Nfft4GPAmdFeatureGpLooBind": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "Nfft4GPAmdFeatureGpLooLoss": (C.c_int, [vp, vp, vp, vp]),
+    "Nfft4GPAmdFeatureGpLooPredict": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, vp, vp,
+                                                C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdFeatureGpLooStatus": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
     "Nfft4GPAmdFeatureGpFree": (None, [vp]),
     "Nfft4GPAmdHostLuLogdet": (C.c_int, [vp, C.c_int, dp, ip]),
     "Nfft4GPAmdDebugGivensLsq": (C.c_int, [C.c_int, C.c_double, vp, C.c_int, C.c_double, vp, vp, vp, ip]),

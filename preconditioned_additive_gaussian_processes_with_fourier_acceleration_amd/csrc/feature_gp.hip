@@ -17,12 +17,15 @@
 // Internally the slots are padded as in model.hip (36 per window, windows to a multiple of 4): a padded slot has
 // zero weight and zero features, B keeps mu on its diagonal there, and (R_p - R) log mu leaves the factor's
 // log-determinant again.
+// The leave-one-out loss, gradient and per-point predictions (k_fgp_loo, further down) need diag(A^{-1}): one
+// quadratic form per training point with an R x R matrix, on the walk of k_model_std.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "internal.h"
+#include "quad_walk.hpp"
 
 namespace nfft4gp_amd {
 namespace {
@@ -56,14 +59,37 @@ struct FeatureGp {
    double* d_vec = nullptr;   // [7][R_p]: w, w', v, G v, w o u, column sums of the trace, 8 scalars
    unsigned int* d_cnt = nullptr;
    size_t cnt_cap = 0;
+   // leave-one-out (Nfft4GPAmdFeatureGpLooBind): the data, borrowed device arrays or copies the object owns
+   const double* loo_X = nullptr;
+   const double* loo_y = nullptr;
+   long long loo_ld = 0;
+   double *loo_Xown = nullptr, *loo_yown = nullptr;
+   double* d_looQ = nullptr;     // [3][R_p][R_p] sym(B^{-1} W), Q_l, Q_G, then two R_p x R_p scratch matrices
+   double* d_loocoef = nullptr;  // [3][R_p] v, c_l, c_mu
+   double* d_loopart = nullptr;  // [blocks + 1][kLooSums] per-workgroup sums; the last row their sum
+   size_t loopart_cap = 0;
+   long long loo_nonpositive = 0;  // points with m_i <= 0 at the last leave-one-out evaluation
 };
 enum { kVw = 0, kVdw, kVv, kVgv, kVwu, kVpart, kVscal };
+// a workgroup's sums: the loss terms, the three gradient terms, the points with m_i <= 0, the points outside the domain
+constexpr int kLooSums = 6;
+
+void loo_unbind(FeatureGp* F)
+{
+   for (double* p : {F->loo_Xown, F->loo_yown})
+      if (p) (void)hipFree(p);
+   F->loo_Xown = F->loo_yown = nullptr;
+   F->loo_X = F->loo_y = nullptr;
+   F->loo_ld = 0;
+}
 
 void fgp_free(FeatureGp* F)
 {
    if (!F) return;
+   loo_unbind(F);
    for (void* p : {(void*)F->d_centre, (void*)F->d_scale, (void*)F->d_feature, (void*)F->d_G, (void*)F->d_by,
-                   (void*)F->d_B, (void*)F->d_Binv, (void*)F->d_piv, (void*)F->d_vec, (void*)F->d_cnt})
+                   (void*)F->d_B, (void*)F->d_Binv, (void*)F->d_piv, (void*)F->d_vec, (void*)F->d_cnt,
+                   (void*)F->d_looQ, (void*)F->d_loocoef, (void*)F->d_loopart})
       if (p) (void)hipFree(p);
    delete F;
 }
@@ -356,6 +382,221 @@ int fgp_apply(FeatureGp* F, const double* coef, const double* X, int n, long lon
    return rc;
 }
 
+// ---- leave-one-out -------------------------------------------------------------------------------
+// With P = B^{-1} W and phi a training point's features: [M^{-1}]_ii = m_i = (1 - phi^T P phi) / mu and
+// [M^{-1} y]_i = a_i = (y_i - phi^T v) / mu (Z^T M^{-1} e_i = B^{-T} phi).  The point's leave-one-out mean is
+// y_i - a_i / m_i, its variance f^2 / m_i, and the loss 1/(2n) sum_i log(f^2 / |m_i|) + a_i^2 / (f^2 m_i) + log 2 pi.
+//   dm_i/dl  = -phi^T Q_l phi,  Q_l = B^{-1} diag(w') B^{-T}        da_i/dl  = -phi^T c_l,  c_l = B^{-1} (w' o u)
+//   dm_i/dmu = -(1 - 2 p_i + phi^T Q_G phi) / mu^2,  Q_G = P^T G P   da_i/dmu = -(a_i - phi^T c_mu) / mu,
+//   c_mu = B^{-1} (w o u)
+// so an evaluation is three symmetric quadratic forms and three linear forms per point.  m_i can be <= 0 (the
+// operator is not always definite): log |m_i|, the signed m_i elsewhere, and such points are counted.
+
+// Q0 = the symmetric part of B^{-1} W; T1 = B^{-T}; T2 = diag(w') B^{-T} (all R_p x R_p column-major)
+__global__ void k_fgp_loo_mats(const double* __restrict__ Binv, const double* __restrict__ w,
+                               const double* __restrict__ dw, int Rp, double* __restrict__ Q0,
+                               double* __restrict__ T1, double* __restrict__ T2)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i >= Rp) return;
+   const size_t e = i + (size_t)j * Rp;
+   const double bij = Binv[e], bji = Binv[j + (size_t)i * Rp];
+   Q0[e] = 0.5 * (bij * w[j] + bji * w[i]);
+   T1[e] = bji;
+   T2[e] = dw[i] * bji;
+}
+
+// T = B^{-1} W
+__global__ void k_fgp_loo_scale(const double* __restrict__ Binv, const double* __restrict__ w, int Rp,
+                                double* __restrict__ T)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i >= Rp) return;
+   const size_t e = i + (size_t)j * Rp;
+   T[e] = Binv[e] * w[j];
+}
+
+// Q <- (Q + Q^T) / 2 in place: the thread of (i, j), i < j, writes both entries
+__global__ void k_fgp_loo_symmetrise(double* __restrict__ Q, int Rp)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+   if (i >= j) return;
+   const size_t e = i + (size_t)j * Rp, et = j + (size_t)i * Rp;
+   const double v = 0.5 * (Q[e] + Q[et]);
+   Q[e] = v;
+   Q[et] = v;
+}
+
+// coef = [v | w' o u | w o u], u = (b - G v) / mu: the right-hand sides of c_l and c_mu behind v
+__global__ void k_fgp_loo_rhs(const double* __restrict__ b, const double* __restrict__ dw,
+                              const double* __restrict__ v, const double* __restrict__ Gv,
+                              const double* __restrict__ wu, int Rp, double mu, double* __restrict__ coef)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= Rp) return;
+   coef[i] = v[i];
+   coef[Rp + i] = dw[i] * ((b[i] - Gv[i]) / mu);
+   coef[2 * (size_t)Rp + i] = wu[i];
+}
+
+// k_fgp_loo: one pass over the n training points, 128 per workgroup.  The three matrices of Q (sym P, Q_l, Q_G;
+// R_p^2 apart) are walked one after another by quad_walk.hpp's walk (k_model_std's: an S tile and its feature panel
+// already fill the LDS, so there is no room for three tiles against one panel, and three tiles' accumulators do not
+// fit the registers); the first walk's epilogue, which generates every window's features once per point, also dots
+// them with v, c_l and c_mu, a quarter of a window per thread.  A point's six sums run in a fixed order that depends
+// on neither its place in the batch nor n.  The epilogue forms the point's loss term and three gradient terms
+// (before dt and 1 / 2n) and, when asked, its leave-one-out mean and variance; the workgroup's kLooSums sums fold
+// over the wave in a fixed butterfly, then over the waves in wave order; sum_parts_dev adds the workgroups in block
+// order.  No atomics.  A point outside a window's domain (the wrong X was bound) is counted and the caller refuses:
+// mv_angle gives it the angle 0, so nothing is NaN.
+__global__ __launch_bounds__(kMsThreads) void k_fgp_loo(const double* __restrict__ Q, int Rp,
+                                                        const double* __restrict__ coef,
+                                                        const double* __restrict__ centre,
+                                                        const double* __restrict__ scale,
+                                                        const int* __restrict__ feature, int nw,
+                                                        const double* __restrict__ X, long long ldim, int n,
+                                                        const double* __restrict__ y, double f, double mu,
+                                                        double* __restrict__ mean_out, double* __restrict__ var_out,
+                                                        double* __restrict__ part_out)
+{
+   extern __shared__ double m_smem[];
+   __shared__ double s_q[3][kMsPts];
+   __shared__ double s_red[kMsThreads / kWave][kLooSums];
+   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int p = tid & (kMsPts - 1), part = tid >> 7;
+   const long long ip = (long long)blockIdx.x * kMsPts + p;
+   const bool live = ip < n;
+   quad_zero_pad(m_smem);
+   const QuadPoints P{centre, scale, feature, nw, X, ldim, ip, live};
+   double lin[3] = {0.0, 0.0, 0.0};
+   for (int m = 0; m < 3; m++) {
+      const double psum = quad_walk<3>(Q + (size_t)m * Rp * Rp, Rp, P, m_smem, m == 0, coef, Rp, lin);
+      quad_fold(psum, s_q[m]);
+   }
+   __syncthreads();  // the last walk has left the buffers
+   double* s_lin = m_smem;  // [form][part][point]
+#pragma unroll
+   for (int q = 0; q < 3; q++) s_lin[(q * 4 + part) * kMsPts + p] = lin[q];
+   __syncthreads();
+   double t[kLooSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+   if (part == 0 && live) {  // waves 0 and 1 own the 128 points from here; the others add exact zeros
+      bool outside = false;
+      for (int c = 0; c < nw; c++) {
+         const double xs = (X[(size_t)feature[c] * (size_t)ldim + ip] - centre[c]) * scale[c];
+         outside = outside || !(fabs(xs) <= kMpLimit);
+      }
+      double l3[3];
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+         const double* sl = s_lin + q * 4 * kMsPts + p;
+         l3[q] = ((sl[0] + sl[kMsPts]) + sl[2 * kMsPts]) + sl[3 * kMsPts];
+      }
+      const double pi = s_q[0][p], ql = s_q[1][p], qg = s_q[2][p];
+      const double ff = f * f, yi = y[ip];
+      const double mi = (1.0 - pi) / mu, ai = (yi - l3[0]) / mu;
+      const double dm_l = -ql, da_l = -l3[1];
+      const double dm_mu = -((1.0 - 2.0 * pi) + qg) / (mu * mu), da_mu = -(ai - l3[2]) / mu;
+      const double aa = ai * ai, ffm = ff * mi;
+      t[0] = log(ff / fabs(mi)) + aa / ffm + 1.8378770664093454835606594728112;  // log 2 pi
+      t[1] = 2.0 / f - 2.0 * aa / (ffm * f);
+      t[2] = -dm_l / mi + 2.0 * ai * da_l / ffm - aa * dm_l / (ffm * mi);
+      t[3] = -dm_mu / mi + 2.0 * ai * da_mu / ffm - aa * dm_mu / (ffm * mi);
+      t[4] = mi <= 0.0 ? 1.0 : 0.0;  // the counts are exact in a double
+      t[5] = outside ? 1.0 : 0.0;
+      if (mean_out) mean_out[ip] = yi - ai / mi;
+      if (var_out) var_out[ip] = ff / mi;
+   }
+#pragma unroll
+   for (int k = 0; k < kLooSums; k++) {
+      double v = t[k];
+#pragma unroll
+      for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      if (lane == 0) s_red[wave][k] = v;
+   }
+   __syncthreads();
+   if (tid < kLooSums) {
+      double v = 0.0;
+      for (int w = 0; w < kMsThreads / kWave; w++) v += s_red[w][tid];
+      part_out[(size_t)blockIdx.x * kLooSums + tid] = v;
+   }
+}
+
+// The leave-one-out sums (kLooSums, host) at (f, l, mu) over the bound data; d_mean / d_var (device, n; may be NULL)
+// receive the per-point mean and variance.  The object's factor at (l, mu) is fgp_factor's: shared, not rebuilt.
+int fgp_loo(FeatureGp* F, double f, double l, double mu, double* d_mean, double* d_var, double* sums)
+{
+   if (fgp_factor(F, l, mu)) return -1;
+   hipStream_t s = current_stream();
+   const int Rp = F->Rp, n = F->n;
+   const size_t rr = (size_t)Rp * Rp;
+   const size_t nblk = ((size_t)n + kMsPts - 1) / kMsPts;
+   if (!F->d_looQ) {  // at 128 windows 5 x 170 MB, as long as the object lives
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_looQ, sizeof(double) * 5 * rr));
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_loocoef, sizeof(double) * 3 * (size_t)Rp));
+   }
+   if (nblk + 1 > F->loopart_cap) {
+      if (F->d_loopart) (void)hipFree(F->d_loopart);
+      F->d_loopart = nullptr;
+      F->loopart_cap = 0;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_loopart, sizeof(double) * (nblk + 1) * kLooSums));
+      F->loopart_cap = nblk + 1;
+   }
+   double* V = F->d_vec;
+   auto vec = [&](int which) { return (const double*)(V + (size_t)which * Rp); };
+   double *Q0 = F->d_looQ, *Ql = Q0 + rr, *Qg = Q0 + 2 * rr, *T1 = Q0 + 3 * rr, *T2 = Q0 + 4 * rr;
+   const dim3 g2((Rp + 255) / 256, Rp);
+   hipLaunchKernelGGL(k_fgp_loo_mats, g2, dim3(256), 0, s, (const double*)F->d_Binv, vec(kVw), vec(kVdw), Rp, Q0, T1,
+                      T2);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (gemm_f64(true, Rp, Rp, Rp, T1, Rp, T2, Rp, Ql, Rp, s)) return -1;  // B^{-1} diag(w') B^{-T}
+   hipLaunchKernelGGL(k_fgp_loo_scale, g2, dim3(256), 0, s, (const double*)F->d_Binv, vec(kVw), Rp, T1);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (gemm_f64(false, Rp, Rp, Rp, F->d_G, Rp, T1, Rp, T2, Rp, s)) return -1;  // G P
+   if (gemm_f64(true, Rp, Rp, Rp, T1, Rp, T2, Rp, Qg, Rp, s)) return -1;       // P^T G P
+   hipLaunchKernelGGL(k_fgp_loo_symmetrise, g2, dim3(256), 0, s, Ql, Rp);
+   hipLaunchKernelGGL(k_fgp_loo_symmetrise, g2, dim3(256), 0, s, Qg, Rp);
+   hipLaunchKernelGGL(k_fgp_loo_rhs, dim3((Rp + 255) / 256), dim3(256), 0, s, (const double*)F->d_by, vec(kVdw),
+                      vec(kVv), vec(kVgv), vec(kVwu), Rp, mu, F->d_loocoef);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   // c_l and c_mu through the factors' substitution, as v is (fgp_factor's note on the residual)
+   if (lu_resolve_dev(F->d_B, Rp, F->d_piv, F->d_loocoef + Rp, 2, s)) return -1;
+   static const bool attr = []() {
+      (void)hipFuncSetAttribute((const void*)k_fgp_loo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMsLds);
+      (void)hipGetLastError();
+      return true;
+   }();
+   (void)attr;
+   hipLaunchKernelGGL(k_fgp_loo, dim3((unsigned int)nblk), dim3(kMsThreads), kMsLds, s, (const double*)Q0, Rp,
+                      (const double*)F->d_loocoef, (const double*)F->d_centre, (const double*)F->d_scale,
+                      (const int*)F->d_feature, F->nw, F->loo_X, F->loo_ld, n, F->loo_y, f, mu, d_mean, d_var,
+                      F->d_loopart);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (sum_parts_dev(F->d_loopart, (int)nblk, kLooSums, F->d_loopart + nblk * kLooSums, s)) return -1;
+   NFFT4GP_HIP_CHECK(hipMemcpyAsync(sums, F->d_loopart + nblk * kLooSums, sizeof(double) * kLooSums,
+                                    hipMemcpyDeviceToHost, s));
+   NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+   return 0;
+}
+
+// what the three leave-one-out entry points refuse alike; 0 when the evaluation may go on
+int loo_ready(const FeatureGp* F, const char* who, double f)
+{
+   if (!F->loo_X || !F->loo_y) {
+      fprintf(stderr, "nfft4gp_amd: %s: no data is bound (Nfft4GPAmdFeatureGpLooBind).\n", who);
+      return -1;
+   }
+   if (!std::isfinite(f) || f == 0.0) return -1;
+   return 0;
+}
+
+int loo_outside(const FeatureGp* F, const char* who, double count)
+{
+   if (count == 0.0) return 0;
+   fprintf(stderr, "nfft4gp_amd: %s: %.0f of %d bound rows lie outside the domain: X is not the data the object was "
+                   "created over.\n", who, count, F->n);
+   return -1;
+}
+
 }  // namespace
 }  // namespace nfft4gp_amd
 
@@ -620,6 +861,97 @@ int Nfft4GPAmdFeatureGpStatus(void* fgp, int* det_sign, double* logabsdet)
    if (!F) return -1;
    if (det_sign) *det_sign = F->det_sign;
    if (logabsdet) *logabsdet = F->logabsdet;
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpLooBind(void* fgp, const double* X, int n, int ldim, int d, const double* y)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F) return -1;
+   (void)hipStreamSynchronize(current_stream());  // nothing in flight reads the buffers that go
+   loo_unbind(F);
+   if (!X) return 0;
+   if (!y || n != F->n || d != F->d || ldim < n) {
+      fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdFeatureGpLooBind: n and d must be the object's (%d, %d), ldim >= n, and "
+                      "y given.\n", F->n, F->d);
+      return -1;
+   }
+   hipStream_t s = current_stream();
+   const double* dy = nullptr;
+   long long ldy;
+   int rc = stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &F->loo_X, &F->loo_ld, &F->loo_Xown);
+   if (!rc) rc = stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &F->loo_yown);
+   if (hipStreamSynchronize(s) != hipSuccess) rc = -1;  // the host arrays may go after the call
+   F->loo_y = dy;
+   if (rc) loo_unbind(F);
+   return rc;
+}
+
+int Nfft4GPAmdFeatureGpLooLoss(void* fgp, double* x, double* lossp, double* dloss)
+{
+   const char* who = "Nfft4GPAmdFeatureGpLooLoss";
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || !x || !lossp || !dloss) return -1;
+   double t[3], dt[3];
+   for (int i = 0; i < 3; i++)
+      if (Nfft4GPTransform((nfft4gp_transform_type)F->transform, x[i], 0, t + i, dt + i)) return -1;
+   const double f = t[0], l = t[1], mu = t[2];
+   if (!(mu > 0.0) || loo_ready(F, who, f)) return -1;
+   double sums[kLooSums];
+   if (fgp_loo(F, f, l, mu, nullptr, nullptr, sums) || loo_outside(F, who, sums[5])) return -1;
+   F->loo_nonpositive = (long long)sums[4];
+   const double half = 0.5 / (double)F->n;
+   const double loss = half * sums[0];
+   double g[3];
+   bool finite = std::isfinite(loss);
+   for (int i = 0; i < 3; i++) {
+      g[i] = half * sums[1 + i] * dt[i];
+      finite = finite && std::isfinite(g[i]);
+      if (F->has_mask && !F->mask[i]) g[i] = 0.0;
+   }
+   if (!finite) return -1;
+   *lossp = loss;
+   for (int i = 0; i < 3; i++) dloss[i] = g[i];
+   return 0;
+}
+
+int Nfft4GPAmdFeatureGpLooPredict(void* fgp, double f, double l, double mu, double* mean, double* var,
+                                  long long* n_nonpositive)
+{
+   const char* who = "Nfft4GPAmdFeatureGpLooPredict";
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || loo_ready(F, who, f)) return -1;
+   hipStream_t s = current_stream();
+   const size_t bytes = sizeof(double) * (size_t)F->n;
+   double* own[2] = {nullptr, nullptr};
+   double* host[2] = {mean, var};
+   double* dev[2] = {mean, var};
+   auto body = [&]() -> int {
+      for (int k = 0; k < 2; k++)
+         if (host[k] && !is_device_ptr(host[k])) {
+            NFFT4GP_HIP_CHECK(hipMalloc((void**)&own[k], bytes));
+            dev[k] = own[k];
+         }
+      double sums[kLooSums];
+      if (fgp_loo(F, f, l, mu, dev[0], dev[1], sums) || loo_outside(F, who, sums[5])) return -1;
+      for (int k = 0; k < 2; k++)
+         if (own[k]) NFFT4GP_HIP_CHECK(hipMemcpyAsync(host[k], own[k], bytes, hipMemcpyDeviceToHost, s));
+      F->loo_nonpositive = (long long)sums[4];
+      if (n_nonpositive) *n_nonpositive = F->loo_nonpositive;
+      return 0;
+   };
+   const int rc = body();
+   (void)hipStreamSynchronize(s);
+   for (double* p : own)
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
+int Nfft4GPAmdFeatureGpLooStatus(void* fgp, long long* n_nonpositive)
+{
+   FeatureGp* F = (FeatureGp*)fgp;
+   if (!F || !n_nonpositive) return -1;
+   *n_nonpositive = F->loo_nonpositive;
    return 0;
 }
 

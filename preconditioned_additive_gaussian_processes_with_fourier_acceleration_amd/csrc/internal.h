@@ -537,6 +537,8 @@ struct WindowMap {
 // the 33 weights of one window (W's diagonal) and their derivative in l
 void feature_weights(int kernel, double l, double scale, int nw, double* w33);
 void feature_weights_grad(int kernel, double l, double scale, int nw, double* dw33);
+// out[i] = part[0][i] + part[1][i] + ... over nblk rows of count doubles, in row order (k_model_sum_parts; device)
+int sum_parts_dev(const double* part, int nblk, int count, double* out, hipStream_t s);
 // the number of rows of dX (n x d device, ld) with a coordinate outside some window's domain
 int window_count_outside(const WindowMap& W, const double* dX, long long ld, int n, hipStream_t s, long long* outside);
 // G = Z^T Z (R_p x R_p device, column-major) over the n rows of dX, Z formed in chunks whose Grams are added in

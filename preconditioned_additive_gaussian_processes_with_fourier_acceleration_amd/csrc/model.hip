@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "quad_walk.hpp"
 
 namespace nfft4gp_amd {
 namespace {
@@ -244,7 +245,6 @@ int model_predict(Model* M, const double* Xnew, int n_new, long long ldim, doubl
 // (S + S^T) / 2.  Internally a window takes kMvPad = 36 slots (33 features and 3 zeros: a whole number of MFMA k
 // steps) and the windows are padded to a multiple of 4 (k_model_std's column tile), R_p = 36 * 4 ceil(nw / 4); the
 // added slots have zero features and zero weight, so mu I + W G keeps mu on their diagonal and S is zero there.
-typedef double d4 __attribute__((ext_vector_type(4)));
 // (the slot constants, mv_order, mv_angle and mv_rotate are internal.h's: feature_gp.hip shares them)
 
 // per workgroup the number of rows with a coordinate outside some window's domain
@@ -445,6 +445,13 @@ void feature_weights_grad(int kernel, double l, double scale, int nw, double* dw
    weight_map(bh, dscale, nw, dw33);
 }
 
+int sum_parts_dev(const double* part, int nblk, int count, double* out, hipStream_t s)
+{
+   hipLaunchKernelGGL(k_model_sum_parts, dim3((count + 255) / 256), dim3(256), 0, s, part, nblk, count, out);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   return 0;
+}
+
 int window_count_outside(const WindowMap& W, const double* dX, long long ld, int n, hipStream_t s, long long* outside)
 {
    const size_t nblk = ((size_t)n + 255) / 256;
@@ -480,9 +487,7 @@ int window_moments(const WindowMap& W, const double* dX, long long ld, int n, co
          NFFT4GP_HIP_CHECK(hipMalloc((void**)&part, sizeof(double) * (size_t)nblk * (Rp + 1)));
          hipLaunchKernelGGL(k_model_zty, dim3(nblk), dim3(kZyThreads), 0, s, W.centre, W.scale, W.feature, W.nw, dX, ld,
                             n, dy, Rp, part);
-         hipLaunchKernelGGL(k_model_sum_parts, dim3((Rp + 1 + 255) / 256), dim3(256), 0, s, (const double*)part, nblk,
-                            Rp + 1, b);
-         NFFT4GP_HIP_CHECK(hipGetLastError());
+         if (sum_parts_dev(part, nblk, Rp + 1, b, s)) return -1;
          if (!G) {
             NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
             return 0;
@@ -621,27 +626,12 @@ int model_fit_variance(Model* M, const double* X, int n, long long ldim)
 }
 
 // ---- serving: std = sqrt| f^2 (mu + phi^T S phi) | ---------------------------------------------------------------
-// k_model_std: one workgroup owns 128 points and walks S in column tiles of 144 (4 windows); per tile the product
-// Phi S[:, tile] (128 x 144) is accumulated on v_mfma_f64_16x16x4_f64 over k steps of 36 (one window).  The Phi
-// operand is generated into LDS per step: one sincospi per (point, window) and 16 rotations, four threads per
-// point each storing a quarter of the window's features.  8 waves of 16 points x 144 columns (9 MFMA blocks,
-// operands swapped as in k_gemm_f64: a lane holds the columns lane / 16 + 4 reg of 16 consecutive points).  LDS is
-// double-buffered as in k_gemm_f64: step c's MFMAs read buffer c & 1 while step c + 1's rows of S (global loads
-// issued before them) are in flight and its features are generated into the other buffer; one barrier per step.
-// The epilogue regenerates the tile's own 4 windows of features and dots them with the accumulators: Phi and
-// Phi S never reach memory.  S is symmetric, so a tile walks only the windows up to its own and doubles the
-// earlier ones' sum: 144 of 256 k steps at 32 windows.  A point's sum runs over (tile, window, block, register)
-// in a fixed order, then over its 4 lanes in lane order: its bits depend on neither its place in the batch nor
-// the batch size.
+// k_model_std: one workgroup owns 128 points; phi^T S phi is quad_walk.hpp's walk of S on v_mfma_f64_16x16x4_f64
+// (column tiles of 4 windows, k steps of one window, features generated into LDS, the symmetric half-walk, double
+// buffering; a point's bits depend on neither its place in the batch nor the batch size).
 // Measured at n_new = 1e6, 32 windows (tools/model_std_probe.py; profiles/model_std_ab.txt): 28.9 ms, 49 % of the
 // fp64 matrix peak counted at n_new R^2 flops; without the symmetry 50.2 ms; the composed route (a feature kernel,
 // gemm_f64 and a row dot, in chunks) 72.3 ms with the same values to 2e-15.  Both were removed.
-constexpr int kMsPts = 128, kMsCols = 4 * kMvPad, kMsThreads = 512;
-constexpr int kMsLdA = kMsPts + 1, kMsLdB = kMsCols + 1;
-constexpr int kMsBuf = kMvPad * (kMsLdA + kMsLdB);          // doubles per buffer: features, then rows of S
-constexpr size_t kMsLds = sizeof(double) * 2 * kMsBuf;      // 157.8 KB: one workgroup per CU
-constexpr int kMsRowGroups = 6;                             // S fetch: 72 column pairs x 6 row groups of 6 rows
-
 __global__ __launch_bounds__(kMsThreads) void k_model_std(const double* __restrict__ S, int Rp,
                                                           const double* __restrict__ centre,
                                                           const double* __restrict__ scale,
@@ -653,113 +643,15 @@ __global__ __launch_bounds__(kMsThreads) void k_model_std(const double* __restri
    extern __shared__ double m_smem[];
    __shared__ unsigned int s_cnt[kMsThreads / kWave];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   const int wm = wave * 16, lr = lane & 15, lg = lane >> 4;
-   const int p = tid & (kMsPts - 1), part = tid >> 7;  // part: 0 cos 0..8, 1 cos 9..16, 2 sin 1..8, 3 sin 9..16
+   const int p = tid & (kMsPts - 1), part = tid >> 7;
    const long long ip = (long long)blockIdx.x * kMsPts + p;
    const bool live = ip < n_new;
-   const int fcol = 2 * (tid % (kMsCols / 2)), frow = tid / (kMsCols / 2);  // frow >= 6: no part in the S fetch
-   for (int b = 0; b < 2; b++)
-      for (int e = tid; e < (kMvPad - kMvFeat) * kMsLdA; e += kMsThreads) m_smem[b * kMsBuf + kMvFeat * kMsLdA + e] = 0.0;
-   auto xload = [&](int c) { return live ? X[(size_t)feature[c] * (size_t)ldim + ip] : centre[c]; };
-   auto gen = [&](int c, double x, double* As) {  // window c's 33 features of the 128 points into As[feature][point]
-      double c1, s1;
-      (void)mv_angle(x, centre[c], scale[c], c1, s1);
-      double ck = 1.0, sk = 0.0;
-#pragma unroll
-      for (int k = 0; k <= 16; k++) {
-         if (part == (k <= 8 ? 0 : 1)) As[k * kMsLdA + p] = ck;
-         if (k && part == (k <= 8 ? 2 : 3)) As[(16 + k) * kMsLdA + p] = sk;
-         mv_rotate(ck, sk, c1, s1);
-      }
-   };
-   double2 bv[kMvPad / kMsRowGroups];
-   double psum = 0.0;
-   const int ntile = Rp / kMsCols;
-   for (int t = 0; t < ntile; t++) {
-      auto fetch = [&](int c) {  // rows 36 c .. 36 c + 35 of S, the tile's 144 columns (R_p is a whole number of tiles)
-         const double* Sc = S + (size_t)(c * kMvPad + frow) * Rp + t * kMsCols + fcol;
-         if (frow < kMsRowGroups) {
-#pragma unroll
-            for (int u = 0; u < kMvPad / kMsRowGroups; u++)
-               bv[u] = *reinterpret_cast<const double2*>(Sc + (size_t)u * kMsRowGroups * Rp);
-         }
-      };
-      auto store = [&](double* Bs) {
-         if (frow < kMsRowGroups) {
-#pragma unroll
-            for (int u = 0; u < kMvPad / kMsRowGroups; u++) {
-               Bs[(frow + u * kMsRowGroups) * kMsLdB + fcol] = bv[u].x;
-               Bs[(frow + u * kMsRowGroups) * kMsLdB + fcol + 1] = bv[u].y;
-            }
-         }
-      };
-      d4 acc[9];
-#pragma unroll
-      for (int j = 0; j < 9; j++) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
-      __syncthreads();  // the previous tile's epilogue has left both buffers
-      fetch(0);
-      gen(0, xload(0), m_smem);
-      store(m_smem + kMvPad * kMsLdA);
-      __syncthreads();
-      int cur = 0;
-      const int cend = min(nw, 4 * t + 4);  // S is symmetric: the windows after the tile's own are not walked
-      for (int c = 0; c < cend; c++) {
-         const bool more = c + 1 < cend;
-         if (c == 4 * t) {  // the windows before the tile's own count twice (exact), its own once
-#pragma unroll
-            for (int j = 0; j < 9; j++) acc[j] *= 2.0;
-         }
-         double xn = 0.0;
-         if (more) {
-            fetch(c + 1);  // in flight during this step's MFMAs
-            xn = xload(c + 1);
-         }
-         const double* As = m_smem + cur * kMsBuf;
-         const double* Bs = As + kMvPad * kMsLdA;
-#pragma unroll 3
-         for (int k4 = 0; k4 < kMvPad / 4; k4++) {
-            const int kk = 4 * k4 + lg;
-            const double a = As[kk * kMsLdA + wm + lr];
-            double b[9];
-#pragma unroll
-            for (int j = 0; j < 9; j++) b[j] = Bs[kk * kMsLdB + 16 * j + lr];
-#pragma unroll
-            for (int j = 0; j < 9; j++) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[j], a, acc[j], 0, 0, 0);
-         }
-         if (more) {  // the other buffer: nobody reads it during this step
-            gen(c + 1, xn, m_smem + (cur ^ 1) * kMsBuf);
-            store(m_smem + (cur ^ 1) * kMsBuf + kMvPad * kMsLdA);
-         }
-         __syncthreads();
-         cur ^= 1;
-      }
-      // acc[j][rg] = (Phi S)[point wm + lr][column 144 t + 16 j + lg + 4 rg]; window wl of the tile holds the
-      // columns [36 wl, 36 wl + 36): blocks j = 36 wl / 16 .. (36 wl + 35) / 16
-#pragma unroll
-      for (int wl = 0; wl < 4; wl++) {
-         const int c = 4 * t + wl;
-         if (c < nw) {  // uniform over the workgroup
-            double* As = m_smem + (wl & 1) * kMsBuf;  // its readers of two windows ago are behind the last barrier
-            gen(c, xload(c), As);
-            __syncthreads();
-#pragma unroll
-            for (int j = (kMvPad * wl) / 16; j <= (kMvPad * wl + kMvPad - 1) / 16; j++)
-#pragma unroll
-               for (int rg = 0; rg < 4; rg++) {
-                  const int fj = 16 * j + lg + 4 * rg - kMvPad * wl;
-                  const double phi = (fj >= 0 && fj < kMvPad) ? As[fj * kMsLdA + wm + lr] : 0.0;
-                  psum = fma(acc[j][rg], phi, psum);
-               }
-         }
-      }
-   }
+   quad_zero_pad(m_smem);
+   const QuadPoints Q{centre, scale, feature, nw, X, ldim, ip, live};
+   const double psum = quad_walk<0>(S, Rp, Q, m_smem, false, nullptr, 0, nullptr);
    __syncthreads();
    double* s_q = m_smem + kMvPad * kMsLdA;  // [point]
-   {
-      const double v0 = __shfl(psum, lr), v1 = __shfl(psum, lr + 16), v2 = __shfl(psum, lr + 32),
-                   v3 = __shfl(psum, lr + 48);
-      if (lg == 0) s_q[wm + lr] = ((v0 + v1) + v2) + v3;
-   }
+   quad_fold(psum, s_q);
    __syncthreads();
    bool outside = false;
    if (part == 0 && live) {

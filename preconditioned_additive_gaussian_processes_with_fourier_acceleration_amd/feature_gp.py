@@ -4,6 +4,8 @@ With 1-D windows the operator is A = f^2 (Z W Z^T + mu I) with 33 trigonometric 
 diagonal W depends on the hyperparameters.  ``FeatureGP(op, X, y)`` forms G = Z^T Z, b = Z^T y and y^T y once; every
 ``loss``, ``solve``, ``variance`` and ``predict`` after that is 33 nw x 33 nw work: no Krylov iteration, no probe
 vectors, no pass over the training points (``solve`` and ``predict`` read the points they are given, once).
+``bind(X, y)`` then ``loo`` and ``loo_predict``: the exact leave-one-out loss, its gradient and every training point's
+held-out prediction, one pass over the bound points with three R x R quadratic forms each.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ class FeatureGP:
         self.n, self.nw, self.R, self.kernel, self.d = nn.value, nw.value, R.value, k.value, d
         self.op = op
         self.n_outside = 0
+        self._bound = None
 
     @staticmethod
     def _vector(y):
@@ -71,6 +74,68 @@ class FeatureGP:
         s = C.c_int(0)
         _lib.lib().Nfft4GPAmdFeatureGpStatus(self.h, C.byref(s), None)
         return s.value
+
+    def bind(self, X, y):
+        """Bind the data of the constructor for ``loo`` and ``loo_predict`` (the object does not hold X).  numpy
+        arrays are copied to the device once; torch device tensors are borrowed and kept alive here.
+        ``bind(None, None)`` unbinds."""
+        from .nfft import _check_len, _ptr
+        L = _lib.lib()
+        if X is None:
+            L.Nfft4GPAmdFeatureGpLooBind(self.h, None, 0, 0, 0, None)
+            self._bound = None
+            return
+        Xc, _, xp, _, ld, n, d = FittedModel._points(X)
+        y = self._vector(y)
+        _check_len("y", y, n)
+        if L.Nfft4GPAmdFeatureGpLooBind(self.h, xp, int(n), int(ld), int(d), _ptr(y)[0]) != 0:
+            self._bound = None
+            raise ValueError(f"X must be the {self.n} x {self.d} data the object was created over (see stderr)")
+        self._bound = (Xc, y)  # device tensors are borrowed by the library: alive as long as they are bound
+
+    def loo(self, hyper, transform=0, mask=None):
+        """(loss, grad) of the leave-one-out objective at ``hyper`` = (f, l, mu) before the transform: the negative
+        mean log predictive density of every training point given the others, exact for this operator, with
+        ``loss``'s conventions.  Needs ``bind``; ``n_nonpositive`` counts the points whose [A^{-1}]_ii was <= 0."""
+        L = _lib.lib()
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
+        if L.Nfft4GPAmdFeatureGpSetOptions(self.h, int(transform), m.ctypes.data if m is not None else None) != 0:
+            raise ValueError("unknown transform")
+        x = np.ascontiguousarray(np.asarray(hyper, dtype=np.float64))
+        if x.size != 3:
+            raise ValueError("hyper = (f, l, mu)")
+        loss, grad = np.zeros(1), np.zeros(3)
+        if L.Nfft4GPAmdFeatureGpLooLoss(self.h, x.ctypes.data, loss.ctypes.data, grad.ctypes.data) != 0:
+            raise RuntimeError("Nfft4GPAmdFeatureGpLooLoss failed: nothing bound, a bound row outside the domain, mu or "
+                               "l not positive after the transform, a zero pivot, or a result that is not finite")
+        return float(loss[0]), grad
+
+    def loo_predict(self, f, l, mu):
+        """(mean, var): what each training point would have been predicted as from the other n - 1, and that
+        prediction's variance (of y: with the noise), at the transformed hyperparameters.  numpy when numpy was
+        bound, device tensors when torch device tensors were.  A point with [A^{-1}]_ii <= 0 has a negative
+        variance; ``n_nonpositive`` counts them."""
+        bound = getattr(self, "_bound", None)
+        if bound is None:
+            raise RuntimeError("no data is bound: FeatureGP.bind(X, y) first")
+        if not hasattr(bound[0], "data_ptr"):
+            mean, var = np.empty(self.n), np.empty(self.n)
+            mp, vp = mean.ctypes.data, var.ctypes.data
+        else:
+            import torch
+            mean, var = (torch.empty(self.n, dtype=torch.float64, device=bound[0].device) for _ in range(2))
+            mp, vp = mean.data_ptr(), var.data_ptr()
+        if _lib.lib().Nfft4GPAmdFeatureGpLooPredict(self.h, float(f), float(l), float(mu), mp, vp, None) != 0:
+            raise RuntimeError("Nfft4GPAmdFeatureGpLooPredict failed (see stderr)")
+        return mean, var
+
+    @property
+    def n_nonpositive(self) -> int:
+        """the number of points with [A^{-1}]_ii <= 0 at the last ``loo`` or ``loo_predict`` (the operator is not
+        always definite); they are counted, never folded away"""
+        k = C.c_longlong(0)
+        _lib.lib().Nfft4GPAmdFeatureGpLooStatus(self.h, C.byref(k))
+        return int(k.value)
 
     def solve(self, X, y, f, l, mu, rhs=None):
         """alpha = A^{-1} y at the transformed hyperparameters; X, y the data of the constructor (numpy -> numpy, a
@@ -142,6 +207,7 @@ class FeatureGP:
         if getattr(self, "h", None):
             _lib.lib().Nfft4GPAmdFeatureGpFree(self.h)
             self.h = None
+            self._bound = None
 
     def __del__(self):
         try:

@@ -118,7 +118,7 @@ def gp_predict(X, Xp, windows, nwindows, dwindows, y, hyper, maxits=100, tol=1e-
 
 
 def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, tol=1e-3,
-           op=None, exact=False, **loss_kwargs):
+           op=None, exact=False, objective="mll", **loss_kwargs):
     """Adam on the GP loss, run by the library: Nfft4GPGpProblemSetup carries gp_loss's arguments,
     Nfft4GPOptimizationAdamStep calls Nfft4GPGpProblemLoss and updates the hyperparameters (``hyper0`` = (f, l, mu)
     before the transform), for at most ``steps`` steps or until the gradient norm falls below ``tol``.
@@ -130,7 +130,14 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
     ``exact=True`` (1-D windows): the same Adam entry points step on Nfft4GPAmdFeatureGpLoss instead -- the loss and
     gradient of the operator's finite-rank form, exact and deterministic, with no solve and no probes (of
     ``loss_kwargs`` only transform and mask apply); the kernel is the one ``op`` was last set up with, Gaussian for
-    a new op."""
+    a new op.
+    ``objective``: "mll" (the default), the marginal likelihood above, or "loo" (with ``exact=True`` only): the
+    leave-one-out predictive density of the same operator, Nfft4GPAmdFeatureGpLooLoss over X and y bound to the
+    FeatureGP, through the same Adam entry points."""
+    if objective not in ("mll", "loo"):
+        raise ValueError('objective is "mll" or "loo"')
+    if objective == "loo" and not exact:
+        raise ValueError('objective="loo" needs exact=True: the leave-one-out loss exists in feature space only')
     unknown = set(loss_kwargs) - {"maxits", "nvecs", "rademacher", "transform", "mask", "print_level", "loss_tol"}
     if unknown:
         raise TypeError(f"unknown loss arguments: {sorted(unknown)}")
@@ -169,7 +176,7 @@ def gp_fit(X, windows, nwindows, dwindows, y, hyper0, steps, lr=0.01, beta1=0.9,
     m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
     L = _lib.lib()
     if exact:
-        return _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, m)
+        return _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, m, objective)
     adam = L.Nfft4GPOptimizationAdamCreate()
     prob = L.Nfft4GPGPProblemCreate()
     try:
@@ -216,13 +223,17 @@ def _set_up_once(op, x0, transform):
             raise RuntimeError("the kernel setup failed")
 
 
-def _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, mask):
+def _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transform, mask, objective="mll"):
     _set_up_once(op, x0, transform)
     fgp = FeatureGP(op, X, lab)
     adam = L.Nfft4GPOptimizationAdamCreate()
     try:
+        fn = "Nfft4GPAmdFeatureGpLoss"
+        if objective == "loo":
+            fgp.bind(X, lab)
+            fn = "Nfft4GPAmdFeatureGpLooLoss"
         if L.Nfft4GPAmdFeatureGpSetOptions(fgp.h, int(transform), mask.ctypes.data if mask is not None else None) or \
-                L.Nfft4GPOptimizationAdamSetProblem(adam, _lib.fnptr("Nfft4GPAmdFeatureGpLoss"), fgp.h, 3) or \
+                L.Nfft4GPOptimizationAdamSetProblem(adam, _lib.fnptr(fn), fgp.h, 3) or \
                 L.Nfft4GPOptimizationAdamSetOptions(adam, steps, float(tol), float(beta1), float(beta2), float(eps),
                                                     float(lr)) or \
                 L.Nfft4GPOptimizationAdamInit(adam, x0.ctypes.data):

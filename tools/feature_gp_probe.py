@@ -7,7 +7,9 @@ loss leg's labels):
   3. solve and predict of n_new = 1e6 points at hyperparameters whose factor the object already holds (what follows
      a loss evaluation at them), device pointers;
   4. FeatureGP.model, wall clock (setup of the operator, solve, one refinement step, table, S);
-  5. in the same run, gp_loss at the bench's settings (50 Lanczos steps x 10 probes, tol 1e-6) on the same data and
+  5. the leave-one-out leg: Nfft4GPAmdFeatureGpLooLoss (l moved per call as in 2, so every call factors anew) and
+     Nfft4GPAmdFeatureGpLooPredict with device outputs (the factor held), over the bound training points;
+  6. in the same run, gp_loss at the bench's settings (50 Lanczos steps x 10 probes, tol 1e-6) on the same data and
      operator: the yardstick, wall clock as the bench measures it, and its value beside the exact one.
 
     python tools/feature_gp_probe.py [--n 1000000 --nw 32 --nnew 1000000 --reps 10 --out FILE.json]
@@ -89,6 +91,23 @@ def main():
     res["solve_ms"], res["solve_min_ms"] = timed(solve, a.reps)
     r = yd - op.matsymv(alpha)
     res["solve_residual_against_the_operator"] = float(r.abs().max() / yd.abs().max())
+
+    assert L.Nfft4GPAmdFeatureGpLooBind(fgp.h, Xt.data_ptr(), n, n, nw, yd.data_ptr()) == 0
+
+    def loo_loss():
+        calls[0] += 1
+        return fgp.loo((f, l + 1e-6 * calls[0], mu), transform=3)
+    res["loo_loss_ms"], res["loo_loss_min_ms"] = timed(loo_loss, a.reps)
+    loo, loo_grad = fgp.loo((f, l, mu), transform=3)
+    res["loo_loss"], res["loo_grad"], res["loo_nonpositive"] = loo, [float(g) for g in loo_grad], fgp.n_nonpositive
+    lmean, lvar = (torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(2))
+
+    def loo_predict():
+        assert L.Nfft4GPAmdFeatureGpLooPredict(fgp.h, f, l, mu, lmean.data_ptr(), lvar.data_ptr(), None) == 0
+    res["loo_predict_ms"], res["loo_predict_min_ms"] = timed(loo_predict, a.reps)
+    res["loo_rmse"] = float(torch.sqrt(torch.mean((lmean - yd) ** 2)))
+    assert L.Nfft4GPAmdFeatureGpLooBind(fgp.h, None, 0, 0, 0, None) == 0
+    del lmean, lvar
 
     Xd = torch.tensor(np.ascontiguousarray(Xnew.T), device="cuda")
     mean = torch.empty(nnew, dtype=torch.float64, device="cuda")

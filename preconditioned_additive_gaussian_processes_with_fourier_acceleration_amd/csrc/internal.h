@@ -242,6 +242,9 @@ struct AdditivePlan {
                               // matvecs (k_grid clears what it read)
    // the fused matvec (launch_matvec_fused): -1 the layout decides (pick_fused_grid), 0 / 1 NFFT4GP_AMD_FUSED_GRID
    int fused_grid = -1;
+   // NFFT4GP_AMD_INTERP_TIMELINE=1: the plain fused interpolation leaves four s_memrealtime stamps per workgroup
+   // (tools/timeline_interp.py)
+   int interp_timeline = 0;
    bool cells33 = false;      // every quantised coordinate lies in the 33 cells 48..63, 0..16 (plan_build_points)
    double* d_hsum = nullptr;  // [2][nw][64] the fused matvec's grid sums (the spread's global atomics, as d_gsum); the
                               // one of parity hsum_par is zero between fused matvecs

@@ -580,6 +580,7 @@ void env_layout(AdditivePlan& P)
    if (const char* e = getenv("NFFT4GP_AMD_DET")) P.det = atoi(e) != 0;
    if (const char* e = getenv("NFFT4GP_AMD_PRECISION")) P.rec = atoi(e) == 32 ? 4 : 5;
    if (const char* e = getenv("NFFT4GP_AMD_FUSED_GRID")) P.fused_grid = atoi(e) != 0;
+   if (const char* e = getenv("NFFT4GP_AMD_INTERP_TIMELINE")) P.interp_timeline = atoi(e) != 0;
 }
 
 void* additive_create(double* data, int n_global, int ldim, int d, int* windows, int nwindows, int dwindows, int rb,

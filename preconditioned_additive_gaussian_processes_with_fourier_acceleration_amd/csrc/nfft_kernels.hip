@@ -288,8 +288,9 @@ __device__ __forceinline__ void ep_prefetch(double (&xe)[kEpMax], double (&ye)[k
    }
 }
 
-// the plain epilogue; DOT: returns this thread's part of (y_out, x)
-template <int THREADS, bool DOT>
+// the plain epilogue; DOT: returns this thread's part of (y_out, x); NT: streaming stores of y (k_interp_fg: nothing
+// of the block's y is left dirty in L2 for the kernel boundary to write back, 65.12 -> 64.75 us at config C)
+template <int THREADS, bool DOT, bool NT = false>
 __device__ __forceinline__ double ep_plain(const double (&xe)[kEpMax], const double (&ye)[kEpMax], const double* s_y,
                                            double* __restrict__ y, int base, int nloc, double alpha, double beta,
                                            double f, double mu)
@@ -302,7 +303,10 @@ __device__ __forceinline__ double ep_plain(const double (&xe)[kEpMax], const dou
       if (j >= nloc) break;
       const double v = ff * (s_y[j] + mu * xe[k]);
       const double yo = (beta == 0.0) ? alpha * v : fma(beta, ye[k], alpha * v);
-      y[(size_t)base + j] = yo;
+      if (NT)
+         __builtin_nontemporal_store(yo, y + (size_t)base + j);
+      else
+         y[(size_t)base + j] = yo;
       if (DOT) dacc = fma(yo, xe[k], dacc);
    }
    return dacc;
@@ -1154,7 +1158,7 @@ __global__ __launch_bounds__(THREADS) void k_interp_hl(const uint16_t* __restric
 // launch_spread_grid's, unchanged); wcirc is d_w.  Every workgroup does k_grid's work for itself, on the 42 grid
 // values and 33 cells that matter (kFgSpan, kFgCells), in LDS:
 //   1. stage the nw x 64 sums and the nw x 64 circulant rows (windows 65 doubles apart: the windows of a wave on
-//      different banks) and clear s_y;
+//      different banks) and clear s_y -- these loads go first, the first tile's after them (see the prologue);
 //   2. h = W g on the span: h_c[k] = sum_j w[(k - j) & 63] g_c[j], compact indices k, j = 0..41 (grid index
 //      kFgSpan0 + k).  A thread forms four neighbouring outputs of one window: each step reads one g and one new w
 //      and feeds four FMAs (the other three w of the step were the previous steps' new ones), j ascending.  One
@@ -1173,7 +1177,7 @@ constexpr int kFgQuads = (kFgSpan + 3) / 4;  // 11 output quads cover the span
 constexpr int kFgHs = 4 * kFgQuads + 1;   // a window's h_c row (44 formed, 42 read)
 constexpr int kFgLdsWin = kFgWin + kFgHs + 2 * kFgRow;  // doubles of LDS per window
 
-template <int THREADS, bool DOT = false, int REC = 5>
+template <int THREADS, bool DOT = false, int REC = 5, bool TIMELINE = false>
 __global__ __launch_bounds__(THREADS) void k_interp_fg(
     const uint16_t* __restrict__ meta, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ qarr,
     const int* __restrict__ tile_off, const double* __restrict__ gsum, double* __restrict__ gclear,
@@ -1195,22 +1199,56 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
    const int tid = threadIdx.x;
    const int base = b * B;
    const int nloc = min(B, n - base);
-   TileRegs cur;
+   constexpr int nwaves = THREADS / 64;
+   if (TIMELINE) stamp(0);
    const int t1 = tile_off[(b + 1) * ngroups];
-   int t = tile_at<REC>(cur, meta, lo, qarr, tile_off[b * ngroups] + (tid >> 6), t1);
-   // this thread's column of the tap table for step 3, fetched with the first tile (d = tid % 8 for every window)
+   int t = tile_off[b * ngroups] + (tid >> 6);
+   // The prologue's loads in the order the build needs them.  Vector loads return in order, so whatever the staging
+   // barrier waits for must be older than a tile's 5 KB per wave: the sums and circulant rows first (the first
+   // kFgRegTrips x THREADS / 64 windows, 32 as at config C, stay in registers across the tile's loads and are written
+   // to LDS with those still in flight: s_waitcnt vmcnt(16 .. 18) in the compiled kernel; further windows go through
+   // LDS before the tile is requested), then the tap column of step 3, then the first tile.  With the tile first the
+   // barrier waited for all of it and the build ran after the tile had landed, not beside it: the staging leg of the
+   // stamps 4.3 -> 2.9 us, 65.80 -> 65.12 us per matvec at config C (profiles/interp_fg_prologue.txt).
+   constexpr int kFgRegTrips = 2;
+   const int ns = nw * kNos;
+   double gv[kFgRegTrips], wv[kFgRegTrips];
+#pragma unroll
+   for (int k = 0; k < kFgRegTrips; k++) {
+      const int i = min(tid + k * THREADS, ns - 1);  // a clamped read: no branch between these loads
+      gv[k] = gsum[i];
+      wv[k] = wcirc[i];
+   }
+   // this thread's column of the tap table for step 3 (d = tid % 8 for every window)
    double ct[kTaps];
 #pragma unroll
    for (int tp = 0; tp < kTaps; tp++) ct[tp] = c_taps[tp * kNC + (tid & (kNC - 1))];
-   for (int i = tid; i < nw * kNos; i += THREADS) {
+   for (int i = tid + kFgRegTrips * THREADS; i < ns; i += THREADS) {
       const int o = (i >> 6) * kFgRow + (i & (kNos - 1));
       s_g[o] = gsum[i];
       s_w[o] = wcirc[i];
    }
-   if (b == 0)
-      for (int i = tid; i < nw * kNos; i += THREADS) gclear[i] = 0.0;
+   // The first tile's loads are unconditional -- a wave without a tile (t >= t1) re-reads the workgroup's last one and
+   // never uses it: behind a branch the compiler counts as if they had not been issued, and the staging writes below
+   // would wait for them (vmcnt(10), the tile's first two loads).  t1 >= 1: a fused layout has a point
+   TileRegs cur, nxt;
+   __builtin_amdgcn_sched_barrier(0);
+   load_tile<REC>(cur, meta, lo, qarr, max(min(t, t1 - 1), 0), tid & 63);
+   __builtin_amdgcn_sched_barrier(0);
    for (int i = tid; i < Bp; i += THREADS) s_y[i] = 0.0;
+#pragma unroll
+   for (int k = 0; k < kFgRegTrips; k++) {
+      const int i = tid + k * THREADS;
+      if (i < ns) {
+         const int o = (i >> 6) * kFgRow + (i & (kNos - 1));
+         s_g[o] = gv[k];
+         s_w[o] = wv[k];
+      }
+   }
+   if (b == 0)
+      for (int i = tid; i < ns; i += THREADS) gclear[i] = 0.0;
    __syncthreads();
+   if (TIMELINE) stamp(1);
    for (int it = tid; it < nw * kFgQuads; it += THREADS) {
       const int w = it / kFgQuads, k0 = 4 * (it % kFgQuads);
       const double* gw = s_g + w * kFgRow;
@@ -1230,6 +1268,12 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
       double* hw = s_h + w * kFgHs + k0;
       hw[0] = a0, hw[1] = a1, hw[2] = a2, hw[3] = a3;
    }
+   // A second tile rides across the rest of the build, so the fabric is not idle while every CU computes: requested
+   // here, by the ten waves without a share of the circulant at once and by the others after theirs (64.75 -> 62.93 us).
+   // Requested with the first tile it lengthened the staging leg by 2 us: a wave does not pass a load before the
+   // memory pipeline has taken it, and the staging writes stand behind the loads in program order.  Unconditional, as
+   // the first tile's loads, and dropped by a wave without a second tile.
+   load_tile<REC>(nxt, meta, lo, qarr, max(min(t + nwaves, t1 - 1), 0), tid & 63);
    __syncthreads();
    {
       const int d = tid & (kNC - 1), seg = (tid >> 3) & 3;
@@ -1254,21 +1298,34 @@ __global__ __launch_bounds__(THREADS) void k_interp_fg(
       }
    }
    __syncthreads();
+   if (TIMELINE) stamp(2);
    // the epilogue's x (mu term) and, when beta != 0, y are fetched now, behind the run loop: after the build, whose
    // registers they would otherwise share, and after its barrier, which would wait for them
    double xe[kEpMax], ye[kEpMax];
    ep_prefetch<THREADS>(xe, ye, x, y, base, nloc, beta);
 
-   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + THREADS / 64, t1)) {
-      // meta is comp << 6 | cell; a cell outside the 33 cannot occur (pick_fused_grid), the min keeps the read in s_H
-      const int ci = min((int)((cur.mt + 16u) & 63u), kFgCells - 1);
+   // meta is comp << 6 | cell; a cell outside the 33 cannot occur (pick_fused_grid), the min keeps the read in s_H
+   auto run = [&](const TileRegs& T) {
+      const int ci = min((int)((T.mt + 16u) & 63u), kFgCells - 1);
       double h[kNC];
-      gather_h_lds(h, s_H + (size_t)(cur.mt >> 6) * kFgWin + ci, kFgCells);
-      interp_run<REC, false>(cur, h, 0.0);
+      gather_h_lds(h, s_H + (size_t)(T.mt >> 6) * kFgWin + ci, kFgCells);
+      interp_run<REC, false>(T, h, 0.0);
+   };
+   // the two tiles held across the build, then the one-deep walk (a steady two-deep walk measured 1 % slower)
+   if (t < t1) {
+      run(cur);
+      const int tn = t + nwaves;
+      t = t1;
+      if (tn < t1) {
+         t = tile_at<REC>(cur, meta, lo, qarr, tn + nwaves, t1);
+         run(nxt);
+      }
    }
+   for (; t < t1; t = tile_at<REC>(cur, meta, lo, qarr, t + nwaves, t1)) run(cur);
    __syncthreads();
+   if (TIMELINE) stamp(3);
 
-   const double dacc = ep_plain<THREADS, DOT>(xe, ye, s_y, y, base, nloc, alpha, beta, f, mu);
+   const double dacc = ep_plain<THREADS, DOT, true>(xe, ye, s_y, y, base, nloc, alpha, beta, f, mu);
    if (DOT) ep_dot_finish<THREADS>(dacc, s_scr, dot_part, dot_ticket, dot_out);
 }
 
@@ -1482,8 +1539,11 @@ static InterpPartFn interp_part_fn(int rec) { return rec == 4 ? k_interp_part<51
 typedef void (*InterpFgFn)(const uint16_t*, const uint32_t*, const uint32_t*, const int*, const double*, double*,
                            const double*, const double*, double*, int, int, int, double, double, double, double,
                            double*, unsigned int*, double*, int);
-static InterpFgFn interp_fg_fn(bool dot, int rec)
+// tl: the plain kernel with timeline stamps (NFFT4GP_AMD_INTERP_TIMELINE, tools/timeline_interp.py)
+static InterpFgFn interp_fg_fn(bool dot, int rec, bool tl)
 {
+   if (tl && !dot)
+      return rec == 4 ? k_interp_fg<kInterpThreads, false, 4, true> : k_interp_fg<kInterpThreads, false, 5, true>;
    if (rec == 4) return dot ? k_interp_fg<kInterpThreads, true, 4> : k_interp_fg<kInterpThreads, false, 4>;
    return dot ? k_interp_fg<kInterpThreads, true, 5> : k_interp_fg<kInterpThreads, false, 5>;
 }
@@ -1550,7 +1610,8 @@ static std::vector<const void*> interp_kernels()
          for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp2_fn(det, sm, rec));
    for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp_part_fn(rec));
    for (int d = 0; d < 2; d++)
-      for (int rec = 4; rec <= 5; rec++) v.push_back((const void*)interp_fg_fn(d, rec));
+      for (int rec = 4; rec <= 5; rec++)
+         for (int tl = 0; tl < 2; tl++) v.push_back((const void*)interp_fg_fn(d, rec, tl));
    return v;
 }
 // every spread kernel the launchers pick
@@ -1770,8 +1831,8 @@ int launch_matvec_fused(AdditivePlan& P, double alpha, const double* d_x, double
    double* S = P.d_hsum + (size_t)P.hsum_par * ns;
    double* Sother = P.d_hsum + (size_t)(1 - P.hsum_par) * ns;
    if (launch_spread_to(P, d_x, nullptr, S, stream)) return -1;
-   launch_ev(interp_fg_fn(d_dot != nullptr, P.rec), dim3(P.nblocks), dim3(kInterpThreads), fg_lds_bytes(P.B, P.nw),
-             stream, P.kev ? P.kev + 4 : nullptr, P.dl.meta, P.dl.lo, P.dl.q, P.dl.tile_off, (const double*)S, Sother,
+   launch_ev(interp_fg_fn(d_dot != nullptr, P.rec, P.interp_timeline != 0), dim3(P.nblocks), dim3(kInterpThreads),
+             fg_lds_bytes(P.B, P.nw), stream, P.kev ? P.kev + 4 : nullptr, P.dl.meta, P.dl.lo, P.dl.q, P.dl.tile_off, (const double*)S, Sother,
              (const double*)P.d_w, d_x, d_y, P.n, P.B, P.ngroups, alpha, beta, P.f, P.mu * P.diag, P.d_dot_part,
              P.d_dot_ticket, d_dot, P.nw);
    NFFT4GP_HIP_CHECK(hipGetLastError());

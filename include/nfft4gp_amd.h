@@ -897,6 +897,23 @@ int Nfft4GPAmdModelFitVariance(void *model, const NFFT4GP_DOUBLE *X, int n, int 
  * model holds no variance. */
 int Nfft4GPAmdModelPredictStd(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d,
                               NFFT4GP_DOUBLE *std, int with_noise, long long *n_outside);
+/* The windows one by one: for the windows c in [w0, w0 + wn) and the n_new rows of Xnew,
+ *   effects[(c - w0) ldo + i]    = f^2 Horner(H[c][cell_c], s_c): the value Nfft4GPAmdModelPredict adds for window c
+ *                                  (same decode, same Horner), so their sum over all windows is the mean up to the
+ *                                  rounding of one sum; the constant and the 1/nw belong to the window;
+ *   effect_std[(c - w0) ldo + i] = sqrt| f^2 phi_c^T S_cc phi_c |, S_cc the window's 33 x 33 diagonal block of S: the
+ *                                  posterior standard deviation of window c's term, without a noise term.
+ * Both n_new x wn, column-major with leading dimension ldo >= n_new; either may be NULL (both: only the count).
+ * Pointers host or device; only the columns feature[c] of Xnew for the windows in range are read.  A (point,
+ * window) pair outside that window's domain is NaN in both arrays, the point's other windows are unaffected, and
+ * *n_outside (may be NULL) counts the points with such a pair in the range.  Bits depend on neither a point's
+ * place in the batch nor n_new nor the range.  The constant is shared among the windows and only its sum is
+ * identified by the data, so a window's raw std carries the constant's uncertainty.
+ * 0 (n_new = 0 touches nothing); -3 when effect_std is asked for and the model holds no variance; -1 for a NULL
+ * model, d not the model's, ldim < n_new, ldo < n_new, w0 < 0, wn < 1 or w0 + wn > nw.  A refused call writes
+ * nothing. */
+int Nfft4GPAmdModelPredictEffects(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, int w0, int wn,
+                                  NFFT4GP_DOUBLE *effects, NFFT4GP_DOUBLE *effect_std, int ldo, long long *n_outside);
 /* wall clock of the model's last successful fit in ms: features, Grams and their sum, system + LU + symmetrise */
 int Nfft4GPAmdModelFitTimes(void *model, NFFT4GP_DOUBLE *ms3);
 /* *R = 33 nw when the model holds a variance, else 0 */

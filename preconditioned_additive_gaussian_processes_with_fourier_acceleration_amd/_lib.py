@@ -272,6 +272,8 @@ _SIGS = {
     "Nfft4GPAmdModelFitVariance": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]),
     "Nfft4GPAmdModelPredictStd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                             C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdModelPredictEffects": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
+                                                C.POINTER(C.c_longlong)]),
     "Nfft4GPAmdModelVarianceInfo": (C.c_int, [vp, ip]),
     "Nfft4GPAmdModelFitTimes": (C.c_int, [vp, dp]),
     "Nfft4GPAmdModelVariance": (C.c_int, [vp, vp]),

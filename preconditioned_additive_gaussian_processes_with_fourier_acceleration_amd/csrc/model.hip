@@ -718,6 +718,233 @@ int model_predict_std(Model* M, const double* Xnew, int n_new, long long ldim, d
    return rc;
 }
 
+// ---- the windows one by one: effect[i][c] = f^2 Horner(H_c), effect_std[i][c] = sqrt| f^2 phi_c^T S_cc phi_c | ------
+// f = sum_c g_c is a sum of independent terms a priori; a posteriori g_c(x_c) has mean k_c^T alpha, the value
+// k_model_predict adds for window c, and variance f^2 phi_c^T W_c phi_c - k_c^T A^{-1} k_c = f^2 phi_c^T S_cc phi_c,
+// S_cc the window's 33 x 33 diagonal block of S (no noise term).  The constant b^_0 / nw sits in every window and only
+// the windows' sum of it is identified by the data, so a window's raw std carries the constant's uncertainty.
+//
+// k_model_effects: k_model_predict's walk (the group's tables staged in LDS, one coalesced coordinate load per
+// (point, window), the same decode and Horner) over the windows [w0, w0 + wn), storing each window's ff * v in its
+// own column instead of adding them.  With kStd the point's thread also generates the window's 33 features
+// (mv_angle / mv_rotate: k_model_std's and fit_variance's bits) and forms phi^T S_cc phi over the upper triangle, row
+// by row, the diagonal once and the off-diagonal sum doubled: 561 FMAs and 33 closing steps per (point, window).  S_cc
+// is the same for every lane: the group's blocks are staged in LDS next to its tables (two windows per pass with kStd)
+// and read by broadcast, each read shared by the thread's two points.  A (point, window) pair outside the window's
+// domain is NaN in both columns; the count is of points with any such pair in the range.  No atomics; a point's
+// values depend on neither its place in the batch nor n_new.
+// Measured at n_new = 1e6, 32 windows (tools/model_effects_probe.py, profiles/model_effects_probe.json): effects alone
+// 108.7 us (4.7 TB/s of its 512 MB; k_model_predict 83.5 us in the same run), with std 1.34 ms, 36 % of the fp64 vector
+// peak: the quadratic form's arithmetic and LDS reads, not the streams, set the time.  The form that fetched S_cc by
+// scalar loads from S's own rows (no LDS for S, eight windows per pass) took 1.92 ms against 1.39 ms with the same
+// bits (profiles/model_effects_ab.txt) and was removed; 3 or 4 points per thread and 4 windows per pass were no faster.
+constexpr int kMePts = 2;                  // points per thread with kStd: 2 x 33 features live in registers
+constexpr int kMeBlk = kMvFeat * kMvFeat;  // a window's block of S as staged in LDS
+constexpr int kMeGroup = 2;                // windows per pass with kStd: 2 x (4.1 + 8.7) KB
+
+// quad[p] += phi_p^T B phi_p for a symmetric 33 x 33 block B in LDS (rows of 33, every lane reads the same entry: a
+// broadcast), over its upper triangle row by row; each entry read serves the thread's kPts points
+template <int kPts>
+__device__ inline void effects_quad(const double* blk, const double (&phi)[kPts][kMvFeat], double (&quad)[kPts])
+{
+#pragma unroll
+   for (int j = 0; j < kMvFeat; j++) {
+      const double* row = blk + j * kMvFeat;
+      double t[kPts];
+#pragma unroll
+      for (int p = 0; p < kPts; p++) t[p] = 0.0;
+#pragma unroll
+      for (int k = j + 1; k < kMvFeat; k++) {
+         const double sjk = row[k];
+#pragma unroll
+         for (int p = 0; p < kPts; p++) t[p] = fma(sjk, phi[p][k], t[p]);
+         // at most 8 entries of the block in flight: 164 VGPRs and 3 waves per SIMD; without it 172 and 2, 1.52 ms
+         // against 1.32 ms (profiles/model_effects_ab.txt)
+         if ((k - j) % 8 == 0) __builtin_amdgcn_sched_barrier(0);
+      }
+      const double sjj = row[j];
+#pragma unroll
+      for (int p = 0; p < kPts; p++) quad[p] = fma(phi[p][j], fma(sjj, phi[p][j], 2.0 * t[p]), quad[p]);
+   }
+}
+
+template <bool kStd>
+__global__ __launch_bounds__(kMpThreads) void k_model_effects(
+   const double* __restrict__ H, const double* __restrict__ S, int Rp, const double* __restrict__ centre,
+   const double* __restrict__ scale, const int* __restrict__ feature, int w0, int wn, const double* __restrict__ X,
+   long long ldim, int n_new, double ff, double* __restrict__ effects, double* __restrict__ effect_std, long long lde,
+   long long lds, unsigned int* __restrict__ cnt_out)
+{
+   constexpr int kPts = kStd ? kMePts : kMpPts;
+   constexpr int kGroup = kStd ? kMeGroup : kMpGroup;
+   __shared__ double s_H[kGroup * kMpWin];
+   __shared__ double s_S[kStd ? kGroup * kMeBlk : 1];
+   __shared__ unsigned int s_cnt[kMpThreads / kWave];
+   const int tid = threadIdx.x;
+   const long long base = (long long)blockIdx.x * (kMpThreads * kPts) + tid;
+   bool outside[kPts];
+#pragma unroll
+   for (int p = 0; p < kPts; p++) outside[p] = false;
+   for (int c0 = w0; c0 < w0 + wn; c0 += kGroup) {
+      const int ng = min(kGroup, w0 + wn - c0);
+      if (c0 != w0) __syncthreads();  // every thread has left the previous group's rows
+      {
+         const double2* src = reinterpret_cast<const double2*>(H + (size_t)c0 * kNos * kNC);
+         const int pairs = ng * kNos * kNC / 2;
+         for (int i = tid; i < pairs; i += kMpThreads) {
+            const double2 v = src[i];
+            const int e = 2 * i;  // element of [window][cell][degree]
+            double* row = s_H + (e / (kNos * kNC)) * kMpWin + ((e / kNC) & (kNos - 1));
+            const int dg = e & (kNC - 1);
+            row[dg * kNos] = v.x;
+            row[(dg + 1) * kNos] = v.y;
+         }
+      }
+      if constexpr (kStd)
+         for (int i = tid; i < ng * kMeBlk; i += kMpThreads) {
+            const int cl = i / kMeBlk, e = i - cl * kMeBlk, j = e / kMvFeat, k = e - j * kMvFeat;
+            s_S[i] = S[((size_t)(c0 + cl) * kMvPad + j) * Rp + (size_t)(c0 + cl) * kMvPad + k];
+         }
+      __syncthreads();
+      for (int cl = 0; cl < ng; cl++) {
+         const int c = c0 + cl;
+         const double ctr = centre[c], sc = scale[c];
+         const double* col = X + (size_t)feature[c] * (size_t)ldim;
+         double xv[kPts];
+         bool in[kPts];
+#pragma unroll
+         for (int p = 0; p < kPts; p++) {
+            const long long i = base + (long long)p * kMpThreads;
+            xv[p] = (i < n_new) ? col[i] : ctr;
+         }
+#pragma unroll
+         for (int p = 0; p < kPts; p++) {
+            const long long i = base + (long long)p * kMpThreads;
+            const double xs = (xv[p] - ctr) * sc;         // subtract, then multiply: the setup's two roundings
+            in[p] = fabs(xs) <= kMpLimit;                 // false for NaN and infinities too
+            outside[p] = outside[p] || !in[p];
+            const double xq = in[p] ? xs : 0.0;
+            const uint32_t q = (uint32_t)(unsigned long long)llround(xq * 4294967296.0);  // quantize()
+            const uint32_t cell = q >> 26;
+            const double s = (double)(int)(((q & 0x3FFFFFFu) << 6) ^ 0x80000000u);  // slot_word, no index bits
+            const double* hrow = s_H + cl * kMpWin + cell;
+            double hc[kNC];
+#pragma unroll
+            for (int dg = 0; dg < kNC; dg++) hc[dg] = hrow[dg * kNos];
+            double v = hc[kNC - 1];
+#pragma unroll
+            for (int dg = kNC - 2; dg >= 0; dg--) v = fma(v, s, hc[dg]);
+            if (effects && i < n_new) effects[(size_t)(c - w0) * (size_t)lde + i] = in[p] ? ff * v : __builtin_nan("");
+         }
+         if constexpr (kStd) {
+            double phi[kPts][kMvFeat], quad[kPts];
+#pragma unroll
+            for (int p = 0; p < kPts; p++) {
+               double c1, s1;
+               (void)mv_angle(xv[p], ctr, sc, c1, s1);
+               double ck = 1.0, sk = 0.0;
+#pragma unroll
+               for (int k = 0; k <= 16; k++) {
+                  phi[p][k] = ck;
+                  if (k) phi[p][16 + k] = sk;
+                  mv_rotate(ck, sk, c1, s1);
+               }
+               quad[p] = 0.0;
+            }
+            effects_quad<kPts>(s_S + cl * kMeBlk, phi, quad);
+#pragma unroll
+            for (int p = 0; p < kPts; p++) {  // (all of them before the first store)
+               // the points' forms stay side by side, sharing each entry of the block: without this use the compiler
+               // sinks each point's form into its own guarded store and keeps the whole block live across both
+               asm volatile("" : "+v"(quad[p]));
+            }
+#pragma unroll
+            for (int p = 0; p < kPts; p++) {
+               const long long i = base + (long long)p * kMpThreads;
+               if (i < n_new) effect_std[(size_t)(c - w0) * (size_t)lds + i] = in[p] ? sqrt(fabs(ff * quad[p])) : __builtin_nan("");
+            }
+         }
+      }
+   }
+   if (cnt_out) {
+      unsigned int cnt = 0;
+#pragma unroll
+      for (int p = 0; p < kPts; p++) {
+         const long long i = base + (long long)p * kMpThreads;
+         cnt += (unsigned int)__popcll(__ballot(i < n_new && outside[p]));
+      }
+      if ((tid & (kWave - 1)) == 0) s_cnt[tid / kWave] = cnt;
+      __syncthreads();
+      if (tid == 0) {
+         unsigned int t = 0;
+         for (int w = 0; w < kMpThreads / kWave; w++) t += s_cnt[w];
+         cnt_out[blockIdx.x] = t;
+      }
+   }
+}
+
+int model_predict_effects(Model* M, const double* Xnew, int n_new, long long ldim, int w0, int wn, double* effects,
+                          double* effect_std, long long ldo, long long* n_outside)
+{
+   hipStream_t s = current_stream();
+   const size_t col = sizeof(double) * (size_t)n_new;
+   double *xown = nullptr, *eown = nullptr, *sown = nullptr;
+   auto body = [&]() -> int {
+      const double* dX = Xnew;
+      long long ld = ldim;
+      if (!is_device_ptr(Xnew)) {  // only the columns the windows in range read
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&xown, col * (size_t)M->d));
+         for (int c = w0; c < w0 + wn; c++) {
+            const size_t ft = (size_t)M->feature[c];
+            NFFT4GP_HIP_CHECK(hipMemcpyAsync(xown + ft * (size_t)n_new, Xnew + ft * (size_t)ldim, col,
+                                             hipMemcpyHostToDevice, s));
+         }
+         dX = xown;
+         ld = n_new;
+      }
+      double *de = effects, *ds = effect_std;
+      long long lde = ldo, lds = ldo;
+      const bool ehost = effects && !is_device_ptr(effects), shost = effect_std && !is_device_ptr(effect_std);
+      if (ehost) {
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&eown, col * (size_t)wn));
+         de = eown;
+         lde = n_new;
+      }
+      if (shost) {
+         NFFT4GP_HIP_CHECK(hipMalloc((void**)&sown, col * (size_t)wn));
+         ds = sown;
+         lds = n_new;
+      }
+      const int per = kMpThreads * (effect_std ? kMePts : kMpPts);
+      const size_t nblk = ((size_t)n_new + per - 1) / per;
+      if (n_outside && grow_counts(M, nblk)) return -1;
+      unsigned int* cnt = n_outside ? M->d_cnt : (unsigned int*)nullptr;
+      const dim3 grid((unsigned int)nblk), block(kMpThreads);
+      auto* kern = effect_std ? k_model_effects<true> : k_model_effects<false>;
+      hipLaunchKernelGGL(kern, grid, block, 0, s, (const double*)M->d_H, (const double*)M->d_S, mv_order(M->nw),
+                         (const double*)M->d_centre, (const double*)M->d_scale, (const int*)M->d_feature, w0, wn, dX, ld,
+                         n_new, M->f * M->f, de, ds, lde, lds, cnt);
+      NFFT4GP_HIP_CHECK(hipGetLastError());
+      if (ehost)
+         NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(effects, sizeof(double) * (size_t)ldo, eown, col, col, (size_t)wn,
+                                            hipMemcpyDeviceToHost, s));
+      if (shost)
+         NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(effect_std, sizeof(double) * (size_t)ldo, sown, col, col, (size_t)wn,
+                                            hipMemcpyDeviceToHost, s));
+      if (n_outside) {
+         if (read_counts(M, nblk, s, n_outside)) return -1;
+      } else if (xown || eown || sown) {
+         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+      }
+      return 0;
+   };
+   const int rc = body();
+   if (xown || eown || sown) (void)hipStreamSynchronize(s);
+   for (double* p : {xown, eown, sown})
+      if (p) (void)hipFree(p);
+   return rc;
+}
+
 }  // namespace
 }  // namespace nfft4gp_amd
 
@@ -899,6 +1126,19 @@ int Nfft4GPAmdModelPredictStd(void* model, const double* Xnew, int n_new, int ld
    if (n_new == 0) return 0;
    if (!Xnew || !std_out) return -1;
    return model_predict_std(M, Xnew, n_new, (long long)ldim, std_out, with_noise, n_outside);
+}
+
+int Nfft4GPAmdModelPredictEffects(void* model, const double* Xnew, int n_new, int ldim, int d, int w0, int wn,
+                                  double* effects, double* effect_std, int ldo, long long* n_outside)
+{
+   Model* M = (Model*)model;
+   if (!M || d != M->d || n_new < 0 || ldim < n_new || ldo < n_new) return -1;
+   if (w0 < 0 || wn < 1 || (long long)w0 + wn > M->nw || (n_new > 0 && !Xnew)) return -1;
+   if (effect_std && !M->d_S) return -3;
+   if (n_outside) *n_outside = 0;
+   if (n_new == 0) return 0;
+   return model_predict_effects(M, Xnew, n_new, (long long)ldim, w0, wn, effects, effect_std, (long long)ldo,
+                                n_outside);
 }
 
 int Nfft4GPAmdModelVarianceInfo(void* model, int* R)

@@ -10,7 +10,8 @@
 ``gp_fit``      the reference's training sequence (TESTS/TEST4/foo.cpp:268-347): Nfft4GPGpProblemSetup, then
                 Nfft4GPOptimizationAdam* stepping on Nfft4GPGpProblemLoss.
 ``gp_model``    solve (K + mu I) alpha = y once and keep the result as a model.FittedModel, which predicts new
-                points without the training data.
+                points without the training data (mean, standard deviation, and each window's effect with its
+                own standard deviation: FittedModel.predict_effects / effect_curve).
 """
 from __future__ import annotations
 
@@ -253,7 +254,9 @@ def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, tra
     """The fitted model at the hyperparameters ``hyper`` = (f, l, mu) before the transform: sets the kernel up
     (Gaussian, or the kernel ``op`` was last set up with), solves f^2 (K + mu I) alpha = y with FGMRES on the
     device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse.
-    ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works.
+    ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works, and
+    ``predict_effects(..., std=True)`` / ``effect_curve(..., std=True)``: each window's term with its standard
+    deviation (the terms alone need no variance).
     ``exact=True`` (1-D windows): FeatureGP.model instead -- alpha from the feature-space solve and the variance
     matrix from the same factorisation, no FGMRES (tol, maxits and variance do not apply: S is always loaded)."""
     import torch

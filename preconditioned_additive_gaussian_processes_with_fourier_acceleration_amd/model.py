@@ -5,6 +5,8 @@ nw x 64 x 8 coefficients plus one feature, centre and scale per window -- and ``
 points: no layout of the new points, no solve and no training data.  1-D windows only; points outside the radius
 the training points were scaled to are refused (NaN).  ``fit_variance(X)`` adds the 33 nw x 33 nw matrix S of the
 operator's finite-rank form, after which ``predict_std`` gives the predictive standard deviation the same way.
+The model is additive, f(x) = sum_c g_c(x_c): ``predict_effects`` gives each window's term and, with ``std=True``,
+its posterior standard deviation (S's diagonal blocks), and ``effect_curve`` one window's term along its own feature.
 """
 from __future__ import annotations
 
@@ -111,6 +113,78 @@ class FittedModel:
             raise RuntimeError(f"Nfft4GPAmdModelPredictStd failed with status {rc}")
         self._outside(nout, n_new, strict, "predict_std")
         return std
+
+    def predict_effects(self, Xnew, std: bool = False, strict: bool = True, window=None):
+        """Each window's term of the posterior mean at the rows of Xnew: an (n_new, nw) array whose column c is
+        f^2 times window c's table at the point's coordinate feature[c] -- the value ``predict`` adds for that window,
+        so the columns sum to ``predict`` up to the rounding of one sum.  numpy gives a Fortran-ordered numpy array, a
+        torch device tensor a device tensor (the transpose view of an (nw, n_new) buffer).  ``std=True`` returns the
+        pair (effects, effect_std), effect_std[i, c] = sqrt|f^2 phi_c^T S_cc phi_c| the posterior standard deviation
+        of window c's term without noise (needs ``fit_variance`` or a loaded S).  ``window=c`` returns 1-D results
+        for that window alone and reads only column feature[c].  A (point, window) pair outside the window's domain is
+        NaN and leaves the point's other windows as they are; ``n_outside`` counts the points with such a pair among
+        the windows asked for and ``strict`` raises on them, as in ``predict``.
+
+        The constant is shared among the windows (each carries 1/nw of it) and the data identify only its sum, so a
+        window's raw std includes the constant's uncertainty; effects are not centred on the training data."""
+        if isinstance(Xnew, np.ndarray) or not hasattr(Xnew, "data_ptr"):
+            X = np.asfortranarray(np.asarray(Xnew, dtype=np.float64))
+            torch = None
+        else:
+            import torch
+            if Xnew.dtype != torch.float64:
+                raise ValueError("Xnew must be an n_new x d float64 tensor")
+            X = Xnew.t().contiguous().t() if Xnew.dim() == 2 else Xnew
+        if X.ndim != 2:
+            raise ValueError("Xnew must be n_new x d")
+        n_new, d = X.shape
+        if d != self.d:
+            raise ValueError(f"Xnew has {d} columns; the model was fitted on {self.d}")
+        w0, wn = (0, self.nw) if window is None else (int(window), 1)
+        if not 0 <= w0 < self.nw:
+            raise ValueError(f"window must be in [0, {self.nw})")
+
+        def buffer():
+            if torch is None:
+                a = np.empty((n_new, wn), order="F")
+                return a, a.ctypes.data
+            b = torch.empty((wn, n_new), dtype=torch.float64, device=Xnew.device)
+            return b.t(), b.data_ptr()
+        eff, ep = buffer()
+        sd, sp = buffer() if std else (None, None)
+        nout = C.c_longlong(0)
+        xp = X.ctypes.data if torch is None else X.data_ptr()
+        rc = _lib.lib().Nfft4GPAmdModelPredictEffects(self.h, xp, int(n_new), max(int(n_new), 1), int(d), w0, wn, ep,
+                                                      sp, max(int(n_new), 1), C.byref(nout))
+        if rc == -3:
+            raise RuntimeError("the model holds no variance: call fit_variance(X) first")
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelPredictEffects failed with status {rc}")
+        self._outside(nout, n_new, strict, "predict_effects")
+        if window is not None:
+            eff, sd = eff[:, 0], (sd[:, 0] if std else None)
+        return (eff, sd) if std else eff
+
+    def effect_curve(self, c, values, std: bool = False):
+        """Window c's term at the given values of its own feature (1-D, numpy or a torch device tensor), for plotting:
+        ``predict_effects(X, window=c)`` on an n x d input whose column feature[c] holds the values.  The raw std's
+        caveat about the shared constant applies (see ``predict_effects``)."""
+        c = int(c)
+        if not 0 <= c < self.nw:
+            raise ValueError(f"window must be in [0, {self.nw})")
+        feature = np.empty(self.nw, dtype=np.int32)
+        if _lib.lib().Nfft4GPAmdModelCoefficients(self.h, None, None, None, feature.ctypes.data) != 0:
+            raise RuntimeError("Nfft4GPAmdModelCoefficients failed")
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):
+            v = np.asarray(values, dtype=np.float64).ravel()
+            X = np.zeros((v.size, self.d), order="F")
+            X[:, feature[c]] = v
+        else:
+            import torch
+            v = values.reshape(-1)
+            X = torch.zeros((self.d, v.numel()), dtype=torch.float64, device=values.device).t()
+            X[:, int(feature[c])] = v
+        return self.predict_effects(X, std=std, strict=True, window=c)
 
     def coefficients(self) -> dict:
         """H (nw x 64 x 8), centre, scale, feature (nw each) and the scalars, as numpy arrays."""

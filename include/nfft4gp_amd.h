@@ -931,6 +931,47 @@ int Nfft4GPAmdModelFeatureWeights(int kernel, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE s
  * gradient matvec.  Host only. */
 int Nfft4GPAmdModelFeatureWeightsGrad(int kernel, NFFT4GP_DOUBLE l, NFFT4GP_DOUBLE scale, int nw,
                                       NFFT4GP_DOUBLE *dw33);
+/* ---- joint posterior sample paths of a fitted model -----------------------------------------
+ * The posterior over functions is finite-rank: f(x) = mean(x) + f phi(x)^T theta, theta ~ N(0, S), phi and S as
+ * above.  A draw of theta is a function: evaluated at two point sets it is the same function.  S is not always
+ * positive semidefinite (W has negative entries), so the sampler factors it by a symmetric eigendecomposition
+ * S = V Lambda V^T and drops the negative part: S+ = F F^T, F = V diag(sqrt max(lambda, 0)).  The paths are of the
+ * latent function; observation noise is independent N(0, f^2 mu) per point, for the caller to add.
+ * Nfft4GPAmdModelFitSampler: builds F (deterministic: two calls give the same bits; a refit drops drawn paths).
+ * info3 (may be NULL) receives defect = sum |lambda < 0| / sum |lambda|, lambda_min and lambda_max.  A defect above
+ * rounding (lambda_min < -R 2^-52 lambda_max) means the paths' spread departs from Nfft4GPAmdModelPredictStd, which
+ * keeps the negative part under its | |.  0; -1 NULL model or a failed eigensolve; -3 without a variance.
+ * A later Nfft4GPAmdModelFitVariance / SetVariance frees the factor and the drawn paths. */
+int Nfft4GPAmdModelFitSampler(void *model, NFFT4GP_DOUBLE *info3);
+/* *ms = wall clock of the last sampler fit's eigendecomposition (-4 before a fit) */
+int Nfft4GPAmdModelSamplerFitTime(void *model, NFFT4GP_DOUBLE *ms);
+/* F to the host: R x R, row-major, unpadded, rows in the feature order above, column k belongs to the k-th
+ * smallest eigenvalue (-3 without a variance, -4 before a fit) */
+int Nfft4GPAmdModelSamplerFactor(void *model, NFFT4GP_DOUBLE *F);
+/* Draws ns paths: B = F xi for xi (R x ns, column-major, leading dimension ldxi >= R, host or device) of standard
+ * normals from the caller -- the library has no random number generator.  B stays in the model until the next
+ * draw, so the same paths can be evaluated at any number of point sets.  Column s of B depends on column s of xi
+ * alone, bit for bit.  0; -3 without a variance; -4 before a fit; -1 for a NULL model or xi, ns < 1 or ldxi < R.
+ * A refused call leaves the previous paths in place. */
+int Nfft4GPAmdModelDrawPaths(void *model, const NFFT4GP_DOUBLE *xi, int ns, int ldxi);
+/* *ns = the number of drawn paths, 0 when nothing is drawn */
+int Nfft4GPAmdModelPathsInfo(void *model, int *ns);
+/* B to the host: R x ns, column-major, unpadded (-4 with nothing drawn) */
+int Nfft4GPAmdModelPathWeights(void *model, NFFT4GP_DOUBLE *B);
+/* out[s ldo + i] = mean_i + f sum_j phi_j(x_i) B[j, s] for the n_new rows of Xnew and the ns drawn paths (n_new x ns,
+ * column-major, ldo >= n_new; Xnew and out host or device).  window = -1 sums all windows and mean is
+ * Nfft4GPAmdModelPredict's; window = c gives window c's term of each path around Nfft4GPAmdModelPredictEffects'
+ * column c (the shared constant's caveat applies; only column feature[c] of Xnew matters).  With xi = 0 a path is
+ * that mean to the bit.  A point outside the domain of a window that is summed is NaN in every path and is counted
+ * once in *n_outside (may be NULL).  A value depends on neither the point's place in the batch, nor n_new, nor ns,
+ * nor the path's column.  0 (n_new = 0 touches nothing); -4 with nothing drawn; -1 for a NULL model, d not the
+ * model's, ldim < n_new, ldo < n_new or a window outside [-1, nw).  A refused call writes nothing. */
+int Nfft4GPAmdModelEvalPaths(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, int window,
+                             NFFT4GP_DOUBLE *out, int ldo, long long *n_outside);
+/* measurement only (tools/model_paths_probe.py): all windows' paths at device Xnew into device out by route 0, the
+ * composed route (a feature kernel, Nfft4GPAmdGemm's kernel and an add of the mean, in chunks) */
+int Nfft4GPAmdDebugModelPaths(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int route,
+                              NFFT4GP_DOUBLE *out, int ldo);
 void Nfft4GPAmdModelFree(void *model);
 
 /* ---- the exact GP loss, gradient, solve and variance matrix in feature space -------------------

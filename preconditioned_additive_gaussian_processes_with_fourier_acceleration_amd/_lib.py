@@ -279,6 +279,15 @@ _SIGS = {
     "Nfft4GPAmdModelVariance": (C.c_int, [vp, vp]),
     "Nfft4GPAmdModelSetVariance": (C.c_int, [vp, vp, C.c_int]),
     "Nfft4GPAmdModelFeatureWeights": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
+    "Nfft4GPAmdModelFitSampler": (C.c_int, [vp, vp]),
+    "Nfft4GPAmdModelSamplerFitTime": (C.c_int, [vp, dp]),
+    "Nfft4GPAmdModelSamplerFactor": (C.c_int, [vp, vp]),
+    "Nfft4GPAmdModelDrawPaths": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+    "Nfft4GPAmdModelPathsInfo": (C.c_int, [vp, ip]),
+    "Nfft4GPAmdModelPathWeights": (C.c_int, [vp, vp]),
+    "Nfft4GPAmdModelEvalPaths": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                           C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdDebugModelPaths": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     "Nfft4GPAmdModelFree": (None, [vp]),
     "Nfft4GPAmdModelFeatureWeightsGrad": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
     "Nfft4GPAmdFeatureGpCreate": (vp, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),

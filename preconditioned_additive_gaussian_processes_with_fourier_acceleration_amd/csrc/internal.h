@@ -406,6 +406,8 @@ int gram_tn(int M, int N, int K, const double* A, long long lda, const double* B
             hipStream_t s);
 // ascending eigenvalues of a symmetric device matrix (rocSOLVER dsyevd, no vectors; nystrom.hip)
 int sym_eigvals_dev(double* A, int n, std::vector<double>& w, hipStream_t s);
+// with vectors: A (both triangles valid) becomes the orthonormal eigenvectors as columns (dsyevd, host QL fallback)
+int sym_eig_dev(double* A, int n, std::vector<double>& w, hipStream_t s);
 // the kernel of a preconditioner setup: plain Gaussian / Matern-1/2 of the points' coordinates
 // (Xk == NULL), or the dense additive kernel of the device coordinates Xk (column c of window w at
 // c = w*dw + t, ld ldk; the last window has last_dw of them) -- kernel_eval.hpp

@@ -678,6 +678,50 @@ int sym_eigvals_dev(double* A, int n, std::vector<double>& w, hipStream_t s)
    return sym_eig(h, n, w, V);
 }
 
+// its eigenvector form: A (symmetric, both triangles valid) is overwritten by the orthonormal eigenvectors as columns
+// (column-major), w ascending: rocSOLVER dsyevd with vectors; the host Householder + QL when rocSOLVER did not load.
+// The first call with vectors initialises further parts of rocBLAS, so it runs on the private random() state as the
+// loading does (see rocsolver()): the caller's rand() sequence is untouched.
+int sym_eig_dev(double* A, int n, std::vector<double>& w, hipStream_t s)
+{
+   w.assign(n, 0.0);
+   RocSolver& R = rocsolver();
+   if (R.ok) {
+      static char priv_state[256];
+      char* caller_state = initstate(20240807u, priv_state, sizeof(priv_state));
+      struct Restore {
+         char* s;
+         ~Restore() { setstate(s); }
+      } restore{caller_state};
+      double *d_w = nullptr, *d_e = nullptr;
+      int* d_info = nullptr;
+      int info = 0;
+      int rc = -1;
+      if (dalloc(&d_w, n) == 0 && dalloc(&d_e, n) == 0 && dalloc(&d_info, 1) == 0) {
+         R.set_stream(R.h, s);
+         if (R.syevd(R.h, rocblas_evect_original, rocblas_fill_lower, n, A, n, d_w, d_e, d_info) ==
+                rocblas_status_success &&
+             hipMemcpyAsync(w.data(), d_w, sizeof(double) * n, hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess)
+            rc = info ? -1 : 0;
+      }
+      (void)hipFree(d_w);
+      (void)hipFree(d_e);
+      (void)hipFree(d_info);
+      return rc;
+   }
+   std::vector<double> h((size_t)n * n), V;
+   if (hipMemcpyAsync(h.data(), A, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+       hipStreamSynchronize(s) != hipSuccess)
+      return -1;
+   if (sym_eig(h, n, w, V)) return -1;
+   if (hipMemcpyAsync(A, V.data(), sizeof(double) * V.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
+       hipStreamSynchronize(s) != hipSuccess)
+      return -1;
+   return 0;
+}
+
 // B <- A^{-1} B by LU with partial pivoting (dgetrf / dgetrs semantics; A n x n and B n x nrhs column-major, A
 // overwritten by its factors); returns 0 or the first zero pivot's column + 1.  logabsdet / sign (may be NULL):
 // log |det A| = sum_j log |u_jj| in the order j = 0 .. n - 1, and the sign of det A from the u_jj and the interchanges

@@ -1,6 +1,7 @@
 // quad_walk.hpp -- phi^T S phi for the 128 points of a workgroup on v_mfma_f64_16x16x4_f64, S symmetric R_p x R_p.
 // The body of k_model_std (model.hip), shared with k_fgp_loo (feature_gp.hip), which walks
-// three matrices one after another and also dots the points' features with NLIN coefficient vectors.
+// three matrices one after another and also dots the points' features with NLIN coefficient vectors.  k_model_paths
+// (model.hip) takes the points, the feature generation and the buffers from here for Phi B.
 //
 // One workgroup owns 128 points and walks S in column tiles of 144 (4 windows); per tile the product
 // Phi S[:, tile] (128 x 144) is accumulated over k steps of 36 (one window).  The Phi operand is generated into LDS

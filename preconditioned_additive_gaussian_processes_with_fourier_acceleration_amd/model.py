@@ -7,6 +7,8 @@ the training points were scaled to are refused (NaN).  ``fit_variance(X)`` adds 
 operator's finite-rank form, after which ``predict_std`` gives the predictive standard deviation the same way.
 The model is additive, f(x) = sum_c g_c(x_c): ``predict_effects`` gives each window's term and, with ``std=True``,
 its posterior standard deviation (S's diagonal blocks), and ``effect_curve`` one window's term along its own feature.
+``draw_paths`` / ``paths`` / ``sample`` give joint draws of the latent function from the same S: a draw is a function,
+the same one at every point set it is evaluated at.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ import numpy as np
 from . import _lib
 
 _NCELL, _NC = 64, 8  # cells per window, coefficients per cell (csrc/internal.h kNos, kNC)
+PATHS_TILE = 128     # sample paths a workgroup of k_model_paths holds at once (csrc/model.hip kMqCols)
 
 
 class FittedModel:
@@ -96,6 +99,7 @@ class FittedModel:
             raise ValueError("rows of X lie outside the model's domain (see stderr); the model is unchanged")
         if rc != 0:
             raise RuntimeError(f"Nfft4GPAmdModelFitVariance failed with status {rc} (see stderr)")
+        self.sampler_defect = None  # the factor of the previous S and its paths went with it
         return self
 
     def predict_std(self, Xnew, strict: bool = True, noise: bool = True):
@@ -169,6 +173,10 @@ class FittedModel:
         """Window c's term at the given values of its own feature (1-D, numpy or a torch device tensor), for plotting:
         ``predict_effects(X, window=c)`` on an n x d input whose column feature[c] holds the values.  The raw std's
         caveat about the shared constant applies (see ``predict_effects``)."""
+        return self.predict_effects(self._curve_points(c, values), std=std, strict=True, window=int(c))
+
+    def _curve_points(self, c, values):
+        """an n x d input (numpy, or a device tensor like ``values``) whose column feature[c] holds the values"""
         c = int(c)
         if not 0 <= c < self.nw:
             raise ValueError(f"window must be in [0, {self.nw})")
@@ -184,7 +192,123 @@ class FittedModel:
             v = values.reshape(-1)
             X = torch.zeros((self.d, v.numel()), dtype=torch.float64, device=values.device).t()
             X[:, int(feature[c])] = v
-        return self.predict_effects(X, std=std, strict=True, window=c)
+        return X
+
+    # ---- joint posterior sample paths (Nfft4GPAmdModelFitSampler / DrawPaths / EvalPaths) ----
+    sampler_defect = None  # set by fit_sampler: sum |lambda < 0| / sum |lambda| of S, the share the sampler drops
+
+    def fit_sampler(self):
+        """Factor the variance matrix for sampling: S = V Lambda V^T, F = V sqrt(max(Lambda, 0)), so that F F^T is S
+        without its negative part (S is not always positive semidefinite: the kernel's Fourier coefficients have
+        negative entries at long length scales).  Sets ``sampler_defect`` = sum |lambda < 0| / sum |lambda| and
+        ``sampler_eigen_range`` = (lambda_min, lambda_max); issues a RuntimeWarning when lambda_min < -R 2^-52
+        lambda_max, i.e. beyond the eigensolver's rounding: the paths' spread then departs from ``predict_std``,
+        which keeps the negative part under its absolute value.  Needs ``fit_variance`` (or a loaded S)."""
+        info = (C.c_double * 3)()
+        rc = _lib.lib().Nfft4GPAmdModelFitSampler(self.h, info)
+        if rc == -3:
+            raise RuntimeError("the model holds no variance: call fit_variance(X) first")
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelFitSampler failed with status {rc} (see stderr)")
+        self.sampler_defect = float(info[0])
+        self.sampler_eigen_range = (float(info[1]), float(info[2]))
+        R = 33 * self.nw
+        if info[1] < -R * 2.0 ** -52 * info[2]:
+            import warnings
+            warnings.warn(f"the variance matrix S is indefinite: its negative eigenvalues are {self.sampler_defect:.3e} "
+                          f"of the sum of |eigenvalues| (lambda_min {info[1]:.3e}, lambda_max {info[2]:.3e}) and the "
+                          "sampler drops them, so the spread of the paths departs from predict_std, which keeps the "
+                          "negative part under its absolute value", RuntimeWarning, stacklevel=2)
+        return self
+
+    @property
+    def n_paths(self) -> int:
+        """the number of paths held by the model (0 when nothing is drawn)"""
+        ns = C.c_int(0)
+        if _lib.lib().Nfft4GPAmdModelPathsInfo(self.h, C.byref(ns)) != 0:
+            raise RuntimeError("Nfft4GPAmdModelPathsInfo failed")
+        return ns.value
+
+    def draw_paths(self, n_paths: int, seed=None, xi=None):
+        """Draw ``n_paths`` functions from the joint posterior of the latent function: theta = F xi with xi of
+        standard normals, ``numpy.random.default_rng(seed).standard_normal((33 nw, n_paths))`` unless ``xi`` (that
+        shape; numpy or a float64 device tensor) is given.  The draw stays in the model until the next one, so
+        ``paths`` evaluates the same functions at any number of point sets.  Fits the sampler on first use."""
+        n_paths = int(n_paths)
+        R = 33 * self.nw
+        if n_paths < 1:
+            raise ValueError("n_paths must be at least 1")
+        if xi is None:
+            xi = np.random.default_rng(seed).standard_normal((R, n_paths))
+        if isinstance(xi, np.ndarray) or not hasattr(xi, "data_ptr"):
+            xi = np.asfortranarray(np.asarray(xi, dtype=np.float64))
+            if xi.shape != (R, n_paths):
+                raise ValueError(f"xi must be {R} x {n_paths}")
+            xp = xi.ctypes.data
+        else:
+            import torch
+            if tuple(xi.shape) != (R, n_paths) or xi.dtype != torch.float64:
+                raise ValueError(f"xi must be a {R} x {n_paths} float64 tensor")
+            xi = xi.t().contiguous().t()  # column-major storage
+            xp = xi.data_ptr()
+        L = _lib.lib()
+        rc = L.Nfft4GPAmdModelDrawPaths(self.h, xp, n_paths, R)
+        if rc in (-3, -4):
+            self.fit_sampler()
+            rc = L.Nfft4GPAmdModelDrawPaths(self.h, xp, n_paths, R)
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelDrawPaths failed with status {rc}")
+        return self
+
+    def paths(self, Xnew, window=None, strict: bool = True):
+        """The drawn paths at the rows of Xnew: an (n_new, n_paths) array, column s = predict(Xnew) + f Phi(Xnew) B[:, s]
+        -- a draw of the latent function; observation noise is independent N(0, f^2 mu) per point, for the caller to
+        add.  numpy gives a Fortran-ordered numpy array, a torch device tensor a device tensor (the transpose view of
+        an (n_paths, n_new) buffer).  ``window=c`` gives window c's term of each path around
+        ``predict_effects(window=c)`` (only column feature[c] matters); the caveat about the shared constant from
+        ``predict_effects`` applies to one window's path.  A point outside the domain of a window that is summed is
+        NaN in every path; ``n_outside`` and ``strict`` behave as in ``predict_effects``."""
+        if isinstance(Xnew, np.ndarray) or not hasattr(Xnew, "data_ptr"):
+            X = np.asfortranarray(np.asarray(Xnew, dtype=np.float64))
+            torch = None
+        else:
+            import torch
+            if Xnew.dtype != torch.float64:
+                raise ValueError("Xnew must be an n_new x d float64 tensor")
+            X = Xnew.t().contiguous().t() if Xnew.dim() == 2 else Xnew
+        if X.ndim != 2:
+            raise ValueError("Xnew must be n_new x d")
+        n_new, d = X.shape
+        if d != self.d:
+            raise ValueError(f"Xnew has {d} columns; the model was fitted on {self.d}")
+        w = -1 if window is None else int(window)
+        if window is not None and not 0 <= w < self.nw:
+            raise ValueError(f"window must be in [0, {self.nw})")
+        ns = self.n_paths
+        if ns == 0:
+            raise RuntimeError("the model holds no paths: call draw_paths(n_paths) first")
+        if torch is None:
+            out = np.empty((n_new, ns), order="F")
+            op, xp = out.ctypes.data, X.ctypes.data
+        else:
+            buf = torch.empty((ns, n_new), dtype=torch.float64, device=Xnew.device)
+            out, op, xp = buf.t(), buf.data_ptr(), X.data_ptr()
+        nout = C.c_longlong(0)
+        rc = _lib.lib().Nfft4GPAmdModelEvalPaths(self.h, xp, int(n_new), max(int(n_new), 1), int(d), w, op,
+                                                 max(int(n_new), 1), C.byref(nout))
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelEvalPaths failed with status {rc}")
+        self._outside(nout, n_new, strict, "paths")
+        return out
+
+    def sample(self, Xnew, n_samples: int, seed=None, window=None):
+        """``draw_paths(n_samples, seed)`` then ``paths(Xnew, window)``: joint draws of the latent function at Xnew."""
+        return self.draw_paths(n_samples, seed=seed).paths(Xnew, window=window)
+
+    def path_curve(self, c, values):
+        """Window c's term of every drawn path at the given values of its own feature (1-D, numpy or a torch device
+        tensor): ``effect_curve``'s twin, (n, n_paths).  The caveat about the shared constant applies."""
+        return self.paths(self._curve_points(c, values), window=int(c))
 
     def coefficients(self) -> dict:
         """H (nw x 64 x 8), centre, scale, feature (nw each) and the scalars, as numpy arrays."""

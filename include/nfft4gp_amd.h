@@ -968,10 +968,6 @@ int Nfft4GPAmdModelPathWeights(void *model, NFFT4GP_DOUBLE *B);
  * model's, ldim < n_new, ldo < n_new or a window outside [-1, nw).  A refused call writes nothing. */
 int Nfft4GPAmdModelEvalPaths(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, int window,
                              NFFT4GP_DOUBLE *out, int ldo, long long *n_outside);
-/* measurement only (tools/model_paths_probe.py): all windows' paths at device Xnew into device out by route 0, the
- * composed route (a feature kernel, Nfft4GPAmdGemm's kernel and an add of the mean, in chunks) */
-int Nfft4GPAmdDebugModelPaths(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int route,
-                              NFFT4GP_DOUBLE *out, int ldo);
 void Nfft4GPAmdModelFree(void *model);
 
 /* ---- the exact GP loss, gradient, solve and variance matrix in feature space -------------------

@@ -287,7 +287,6 @@ _SIGS = {
     "Nfft4GPAmdModelPathWeights": (C.c_int, [vp, vp]),
     "Nfft4GPAmdModelEvalPaths": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.POINTER(C.c_longlong)]),
-    "Nfft4GPAmdDebugModelPaths": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     "Nfft4GPAmdModelFree": (None, [vp]),
     "Nfft4GPAmdModelFeatureWeightsGrad": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, vp]),
     "Nfft4GPAmdFeatureGpCreate": (vp, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),

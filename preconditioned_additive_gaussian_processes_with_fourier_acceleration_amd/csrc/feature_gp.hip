@@ -1,6 +1,6 @@
 // feature_gp.hip -- the exact GP loss, its gradient, the solve and the variance matrix in feature space.
 //
-// With 1-D windows the operator is A = f^2 (Z W Z^T + mu I) (model.hip, "the predictive variance"): Z holds 33
+// With 1-D windows the operator is A = f^2 (Z W Z^T + mu I) (model_variance.hip's header): Z holds 33
 // trigonometric features per window of the window's quantised coordinate and W is diagonal.  A handle's centres and
 // scales are fixed at its first setup, so only W depends on the hyperparameters: G = Z^T Z, b = Z^T y and y^T y are
 // formed once per data set (window_moments) and everything after is R x R work, R = 33 nw.  With
@@ -14,8 +14,8 @@
 // w' = dW/dl (feature_weights_grad).  alpha = (y - Z v) / (f^2 mu) solves A alpha = y, S = mu B^{-1} W symmetrised
 // is the matrix of Nfft4GPAmdModelFitVariance, and the posterior mean at a point with features phi is phi^T (w o u).
 // W has negative entries, so B is factored by LU; the loss uses log |det B| and the sign of det B is only reported.
-// Internally the slots are padded as in model.hip (36 per window, windows to a multiple of 4): a padded slot has
-// zero weight and zero features, B keeps mu on its diagonal there, and (R_p - R) log mu leaves the factor's
+// Internally the slots are padded as in model_variance.hip (36 per window, windows to a multiple of 4): a padded slot
+// has zero weight and zero features, B keeps mu on its diagonal there, and (R_p - R) log mu leaves the factor's
 // log-determinant again.
 // The leave-one-out loss, gradient and per-point predictions (k_fgp_loo, further down) need diag(A^{-1}): one
 // quadratic form per training point with an R x R matrix, on the walk of k_model_std.
@@ -57,8 +57,7 @@ struct FeatureGp {
    double* d_Binv = nullptr;  // [R_p][R_p + 1] B^{-1}, then v = B^{-1} (w o b): one solve, R_p + 1 right-hand sides
    int* d_piv = nullptr;      // the factorisation's row interchanges (further right-hand sides: lu_resolve_dev)
    double* d_vec = nullptr;   // [7][R_p]: w, w', v, G v, w o u, column sums of the trace, 8 scalars
-   unsigned int* d_cnt = nullptr;
-   size_t cnt_cap = 0;
+   BlockCounts counts;        // per-workgroup counts of outside points
    // leave-one-out (Nfft4GPAmdFeatureGpLooBind): the data, borrowed device arrays or copies the object owns
    const double* loo_X = nullptr;
    const double* loo_y = nullptr;
@@ -88,7 +87,7 @@ void fgp_free(FeatureGp* F)
    if (!F) return;
    loo_unbind(F);
    for (void* p : {(void*)F->d_centre, (void*)F->d_scale, (void*)F->d_feature, (void*)F->d_G, (void*)F->d_by,
-                   (void*)F->d_B, (void*)F->d_Binv, (void*)F->d_piv, (void*)F->d_vec, (void*)F->d_cnt,
+                   (void*)F->d_B, (void*)F->d_Binv, (void*)F->d_piv, (void*)F->d_vec,
                    (void*)F->d_looQ, (void*)F->d_loocoef, (void*)F->d_loopart})
       if (p) (void)hipFree(p);
    delete F;
@@ -178,7 +177,7 @@ __global__ void k_fgp_variance(const double* __restrict__ Binv, const double* __
 {
    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
    if (j >= R) return;
-   const int ip = i / kMvFeat * kMvPad + i % kMvFeat, jp = j / kMvFeat * kMvPad + j % kMvFeat;
+   const int ip = mv_slot(i), jp = mv_slot(j);
    S[(size_t)i * R + j] = 0.5 * (mu * Binv[ip + (size_t)jp * Rp] * w[jp] + mu * Binv[jp + (size_t)ip * Rp] * w[ip]);
 }
 
@@ -199,7 +198,6 @@ __global__ __launch_bounds__(kFaThreads) void k_fgp_apply(const double* __restri
                                                           double* __restrict__ out, unsigned int* __restrict__ cnt_out)
 {
    extern __shared__ double f_coef[];
-   __shared__ unsigned int s_cnt[kFaThreads / kWave];
    const int tid = threadIdx.x;
    for (int i = tid; i < Rp; i += kFaThreads) f_coef[i] = coef[i];
    __syncthreads();
@@ -236,7 +234,6 @@ __global__ __launch_bounds__(kFaThreads) void k_fgp_apply(const double* __restri
          }
       }
    }
-   unsigned int cnt = 0;
 #pragma unroll
    for (int p = 0; p < kFaPts; p++) {
       const long long i = base + (long long)p * kFaThreads;
@@ -245,33 +242,9 @@ __global__ __launch_bounds__(kFaThreads) void k_fgp_apply(const double* __restri
          const double zc = c * acc[p];
          out[i] = outside[p] ? __builtin_nan("") : (y ? fma(a, y[i], zc) : zc);
       }
-      cnt += (unsigned int)__popcll(__ballot(live && outside[p]));
+      outside[p] = live && outside[p];
    }
-   if (cnt_out) {
-      if ((tid & (kWave - 1)) == 0) s_cnt[tid / kWave] = cnt;
-      __syncthreads();
-      if (tid == 0) {
-         unsigned int t = 0;
-         for (int v = 0; v < kFaThreads / kWave; v++) t += s_cnt[v];
-         cnt_out[blockIdx.x] = t;
-      }
-   }
-}
-
-// a host or device array of rows x cols doubles (leading dimension ld) as a packed device array
-int stage(const double* src, size_t rows, size_t cols, size_t ld, hipStream_t s, const double** dev, long long* dld,
-          double** owned)
-{
-   *owned = nullptr;
-   *dev = src;
-   *dld = (long long)ld;
-   if (is_device_ptr(src)) return 0;
-   NFFT4GP_HIP_CHECK(hipMalloc((void**)owned, sizeof(double) * std::max<size_t>(1, rows * cols)));
-   NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(*owned, sizeof(double) * rows, src, sizeof(double) * ld, sizeof(double) * rows,
-                                      cols, hipMemcpyHostToDevice, s));
-   *dev = *owned;
-   *dld = (long long)rows;
-   return 0;
+   block_count_outside<kFaThreads>(outside, cnt_out);
 }
 
 WindowMap window_map(const FeatureGp* F) { return WindowMap{F->nw, F->d, F->d_centre, F->d_scale, F->d_feature}; }
@@ -331,55 +304,28 @@ int fgp_factor(FeatureGp* F, double l, double mu)
    return 0;
 }
 
-int grow_counts(FeatureGp* F, size_t nblk)
-{
-   if (nblk <= F->cnt_cap) return 0;
-   if (F->d_cnt) (void)hipFree(F->d_cnt);
-   F->d_cnt = nullptr;
-   F->cnt_cap = 0;
-   NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_cnt, sizeof(unsigned int) * nblk));
-   F->cnt_cap = nblk;
-   return 0;
-}
-
 // out = a y + c Z coef at the n rows of X (X, y, out: host or device); *n_outside: the rows outside the domain
 int fgp_apply(FeatureGp* F, const double* coef, const double* X, int n, long long ldim, const double* y, double a,
               double c, double* out, long long* n_outside)
 {
    hipStream_t s = current_stream();
-   double *xown = nullptr, *yown = nullptr, *oown = nullptr;
-   auto body = [&]() -> int {
-      const double *dX, *dy = nullptr;
-      long long ld, ldy;
-      if (stage(X, (size_t)n, (size_t)F->d, (size_t)ldim, s, &dX, &ld, &xown)) return -1;
-      if (y && stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &yown)) return -1;
-      double* dout = out;
-      const bool odev = is_device_ptr(out);
-      if (!odev) {
-         NFFT4GP_HIP_CHECK(hipMalloc((void**)&oown, sizeof(double) * (size_t)n));
-         dout = oown;
-      }
-      const int per = kFaThreads * kFaPts;
-      const size_t nblk = ((size_t)n + per - 1) / per;
-      if (grow_counts(F, nblk)) return -1;
-      hipLaunchKernelGGL(k_fgp_apply, dim3((unsigned int)nblk), dim3(kFaThreads), sizeof(double) * (size_t)F->Rp, s, coef,
-                         F->Rp, (const double*)F->d_centre, (const double*)F->d_scale, (const int*)F->d_feature, F->nw,
-                         dX, ld, n, dy, a, c, dout, F->d_cnt);
-      NFFT4GP_HIP_CHECK(hipGetLastError());
-      if (!odev) NFFT4GP_HIP_CHECK(hipMemcpyAsync(out, oown, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-      std::vector<unsigned int> h(nblk);
-      NFFT4GP_HIP_CHECK(hipMemcpyAsync(h.data(), F->d_cnt, sizeof(unsigned int) * nblk, hipMemcpyDeviceToHost, s));
-      NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
-      long long t = 0;
-      for (unsigned int v : h) t += v;
-      *n_outside = t;
-      return 0;
-   };
-   const int rc = body();
-   (void)hipStreamSynchronize(s);  // nothing in flight reads the staging buffers
-   for (double* p : {xown, yown, oown})
-      if (p) (void)hipFree(p);
-   return rc;
+   Scratch sc(s);
+   const double *dX, *dy = nullptr;
+   long long ld, ldy;
+   if (stage(sc, X, (size_t)n, (size_t)F->d, (size_t)ldim, &dX, &ld)) return -1;
+   if (y && stage(sc, y, (size_t)n, 1, (size_t)n, &dy, &ldy)) return -1;
+   double* dout = out;
+   const bool odev = is_device_ptr(out);
+   if (!odev && sc.alloc(&dout, (size_t)n)) return -1;
+   const int per = kFaThreads * kFaPts;
+   const size_t nblk = ((size_t)n + per - 1) / per;
+   if (F->counts.grow(nblk)) return -1;
+   hipLaunchKernelGGL(k_fgp_apply, dim3((unsigned int)nblk), dim3(kFaThreads), sizeof(double) * (size_t)F->Rp, s, coef,
+                      F->Rp, (const double*)F->d_centre, (const double*)F->d_scale, (const int*)F->d_feature, F->nw, dX,
+                      ld, n, dy, a, c, dout, F->counts.d);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (!odev) NFFT4GP_HIP_CHECK(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+   return F->counts.read(nblk, s, n_outside);  // synchronises: nothing in flight reads the staging buffers
 }
 
 // ---- leave-one-out -------------------------------------------------------------------------------
@@ -480,11 +426,7 @@ __global__ __launch_bounds__(kMsThreads) void k_fgp_loo(const double* __restrict
    __syncthreads();
    double t[kLooSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
    if (part == 0 && live) {  // waves 0 and 1 own the 128 points from here; the others add exact zeros
-      bool outside = false;
-      for (int c = 0; c < nw; c++) {
-         const double xs = (X[(size_t)feature[c] * (size_t)ldim + ip] - centre[c]) * scale[c];
-         outside = outside || !(fabs(xs) <= kMpLimit);
-      }
+      const bool outside = row_outside(centre, scale, feature, nw, X, ldim, ip);
       double l3[3];
 #pragma unroll
       for (int q = 0; q < 3; q++) {
@@ -597,6 +539,36 @@ int loo_outside(const FeatureGp* F, const char* who, double count)
    return -1;
 }
 
+// the device side of a new object: the handle's windows and the moments of (X, y)
+int fgp_fill(FeatureGp* F, const AdditivePlan& P, const char* who, const double* X, int n, int ldim, const double* y)
+{
+   hipStream_t s = current_stream();
+   Scratch sc(s);
+   const int Rp = F->Rp;
+   if (upload(&F->d_centre, P.comp_centre.data(), (size_t)P.nw) ||
+       upload(&F->d_scale, P.comp_scale.data(), (size_t)P.nw) ||
+       upload(&F->d_feature, P.comp_feature.data(), (size_t)P.nw))
+      return -1;
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_G, sizeof(double) * (size_t)Rp * Rp));
+   NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_by, sizeof(double) * ((size_t)Rp + 1)));
+   const double *dX, *dy;
+   long long ld, ldy;
+   if (stage(sc, X, (size_t)n, (size_t)F->d, (size_t)ldim, &dX, &ld) ||
+       stage(sc, y, (size_t)n, 1, (size_t)n, &dy, &ldy))
+      return -1;
+   const WindowMap W = window_map(F);
+   long long outside = 0;
+   if (window_count_outside(W, dX, ld, n, s, &outside)) return -1;
+   if (outside) {
+      fprintf(stderr, "%s: %lld of %d rows of X lie outside the handle's domain: X is not the handle's data.\n", who,
+              outside, n);
+      return -1;
+   }
+   if (window_moments(W, dX, ld, n, dy, F->d_G, F->d_by, F->d_by + Rp, nullptr, s)) return -1;
+   NFFT4GP_HIP_CHECK(hipMemcpy(&F->yy, F->d_by + Rp, sizeof(double), hipMemcpyDeviceToHost));
+   return 0;
+}
+
 }  // namespace
 }  // namespace nfft4gp_amd
 
@@ -648,40 +620,7 @@ void* Nfft4GPAmdFeatureGpCreate(void* additive_handle, const double* X, int n, i
    F->Rp = mv_order(P.nw);
    F->R = kMvFeat * P.nw;
    F->scale = P.comp_scale;
-   hipStream_t s = current_stream();
-   double *xown = nullptr, *yown = nullptr;
-   const int Rp = F->Rp;
-   auto body = [&]() -> int {
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_centre, sizeof(double) * P.nw));
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_scale, sizeof(double) * P.nw));
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_feature, sizeof(int) * P.nw));
-      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_centre, P.comp_centre.data(), sizeof(double) * P.nw, hipMemcpyHostToDevice));
-      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_scale, P.comp_scale.data(), sizeof(double) * P.nw, hipMemcpyHostToDevice));
-      NFFT4GP_HIP_CHECK(hipMemcpy(F->d_feature, P.comp_feature.data(), sizeof(int) * P.nw, hipMemcpyHostToDevice));
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_G, sizeof(double) * (size_t)Rp * Rp));
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&F->d_by, sizeof(double) * ((size_t)Rp + 1)));
-      const double *dX, *dy;
-      long long ld, ldy;
-      if (stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &dX, &ld, &xown) ||
-          stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &yown))
-         return -1;
-      const WindowMap W = window_map(F);
-      long long outside = 0;
-      if (window_count_outside(W, dX, ld, n, s, &outside)) return -1;
-      if (outside) {
-         fprintf(stderr, "%s: %lld of %d rows of X lie outside the handle's domain: X is not the handle's data.\n", who,
-                 outside, n);
-         return -1;
-      }
-      if (window_moments(W, dX, ld, n, dy, F->d_G, F->d_by, F->d_by + Rp, nullptr, s)) return -1;
-      NFFT4GP_HIP_CHECK(hipMemcpy(&F->yy, F->d_by + Rp, sizeof(double), hipMemcpyDeviceToHost));
-      return 0;
-   };
-   const int rc = body();
-   (void)hipStreamSynchronize(s);
-   for (double* p : {xown, yown})
-      if (p) (void)hipFree(p);
-   if (rc) {
+   if (fgp_fill(F, P, who, X, n, ldim, y)) {
       fgp_free(F);
       return NULL;
    }
@@ -754,34 +693,28 @@ int Nfft4GPAmdFeatureGpSolveRhs(void* fgp, const double* X, int n, int ldim, int
    if (fgp_factor(F, l, mu)) return -1;
    hipStream_t s = current_stream();
    const int Rp = F->Rp;
-   double *xown = nullptr, *rown = nullptr, *tmp = nullptr;  // tmp: Z^T r, r^T r, then v in place of w o Z^T r
+   Scratch sc(s);
+   const double *dX, *dr;
+   long long ld, ldr;
+   if (stage(sc, X, (size_t)n, (size_t)d, (size_t)ldim, &dX, &ld) || stage(sc, r, (size_t)n, 1, (size_t)n, &dr, &ldr))
+      return -1;
+   double* tmp;  // Z^T r, r^T r, then v in place of w o Z^T r
+   if (sc.alloc(&tmp, 2 * (size_t)Rp + 1)) return -1;
+   if (window_moments(window_map(F), dX, ld, n, dr, nullptr, tmp, tmp + Rp, nullptr, s)) return -1;
+   double* v = tmp + Rp + 1;
+   hipLaunchKernelGGL(k_fgp_hadamard, dim3((Rp + 255) / 256), dim3(256), 0, s, (const double*)F->d_vec,
+                      (const double*)tmp, Rp, v);
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (lu_resolve_dev(F->d_B, Rp, F->d_piv, v, 1, s)) return -1;
+   const double a = 1.0 / (f * f * mu);
    long long outside = 0;
-   auto body = [&]() -> int {
-      const double *dX, *dr;
-      long long ld, ldr;
-      if (stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &dX, &ld, &xown) ||
-          stage(r, (size_t)n, 1, (size_t)n, s, &dr, &ldr, &rown))
-         return -1;
-      NFFT4GP_HIP_CHECK(hipMalloc((void**)&tmp, sizeof(double) * (2 * (size_t)Rp + 1)));
-      if (window_moments(window_map(F), dX, ld, n, dr, nullptr, tmp, tmp + Rp, nullptr, s)) return -1;
-      double* v = tmp + Rp + 1;
-      hipLaunchKernelGGL(k_fgp_hadamard, dim3((Rp + 255) / 256), dim3(256), 0, s, (const double*)F->d_vec,
-                         (const double*)tmp, Rp, v);
-      NFFT4GP_HIP_CHECK(hipGetLastError());
-      if (lu_resolve_dev(F->d_B, Rp, F->d_piv, v, 1, s)) return -1;
-      const double a = 1.0 / (f * f * mu);
-      return fgp_apply(F, v, dX, n, ld, dr, a, -a, alpha, &outside);
-   };
-   int rc = body();
-   (void)hipStreamSynchronize(s);
-   for (double* p : {xown, rown, tmp})
-      if (p) (void)hipFree(p);
-   if (!rc && outside) {
+   if (fgp_apply(F, v, dX, n, ld, dr, a, -a, alpha, &outside)) return -1;
+   if (outside) {
       fprintf(stderr, "nfft4gp_amd: Nfft4GPAmdFeatureGpSolveRhs: %lld of %d rows of X lie outside the domain.\n", outside,
               n);
-      rc = -2;
+      return -2;
    }
-   return rc;
+   return 0;
 }
 
 int Nfft4GPAmdFeatureGpVariance(void* fgp, double f, double l, double mu, double* S)
@@ -792,18 +725,15 @@ int Nfft4GPAmdFeatureGpVariance(void* fgp, double f, double l, double mu, double
    if (fgp_factor(F, l, mu)) return -1;
    hipStream_t s = current_stream();
    const int R = F->R;
+   Scratch sc(s);
    const bool sdev = is_device_ptr(S);
    double* dS = S;
-   if (!sdev) NFFT4GP_HIP_CHECK(hipMalloc((void**)&dS, sizeof(double) * (size_t)R * R));
+   if (!sdev && sc.alloc(&dS, (size_t)R * R)) return -1;
    hipLaunchKernelGGL(k_fgp_variance, dim3((R + 255) / 256, R), dim3(256), 0, s, (const double*)F->d_Binv,
                       (const double*)F->d_vec, F->Rp, R, mu, dS);
-   int rc = hipGetLastError() == hipSuccess ? 0 : -1;
-   if (!sdev) {
-      if (!rc && hipMemcpyAsync(S, dS, sizeof(double) * (size_t)R * R, hipMemcpyDeviceToHost, s) != hipSuccess) rc = -1;
-      if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
-      (void)hipFree(dS);
-   }
-   return rc;
+   NFFT4GP_HIP_CHECK(hipGetLastError());
+   if (!sdev) NFFT4GP_HIP_CHECK(hipMemcpyAsync(S, dS, sizeof(double) * (size_t)R * R, hipMemcpyDeviceToHost, s));
+   return sc.finish();
 }
 
 int Nfft4GPAmdFeatureGpPredict(void* fgp, double f, double l, double mu, const double* Xnew, int n_new, int ldim, int d,
@@ -828,17 +758,16 @@ int Nfft4GPAmdFeatureGpMoments(void* fgp, double* G, double* b, double* yy)
    FeatureGp* F = (FeatureGp*)fgp;
    if (!F) return -1;
    const int Rp = F->Rp, R = F->R;
-   auto slot = [](int i) { return i / kMvFeat * kMvPad + i % kMvFeat; };
    if (G) {
       std::vector<double> h((size_t)Rp * Rp);
       NFFT4GP_HIP_CHECK(hipMemcpy(h.data(), F->d_G, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
       for (int i = 0; i < R; i++)
-         for (int j = 0; j < R; j++) G[(size_t)i * R + j] = h[(size_t)slot(i) * Rp + slot(j)];
+         for (int j = 0; j < R; j++) G[(size_t)i * R + j] = h[(size_t)mv_slot(i) * Rp + mv_slot(j)];
    }
    if (b) {
       std::vector<double> h((size_t)Rp);
       NFFT4GP_HIP_CHECK(hipMemcpy(h.data(), F->d_by, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-      for (int i = 0; i < R; i++) b[i] = h[slot(i)];
+      for (int i = 0; i < R; i++) b[i] = h[mv_slot(i)];
    }
    if (yy) *yy = F->yy;
    return 0;
@@ -877,14 +806,19 @@ int Nfft4GPAmdFeatureGpLooBind(void* fgp, const double* X, int n, int ldim, int 
       return -1;
    }
    hipStream_t s = current_stream();
-   const double* dy = nullptr;
-   long long ldy;
-   int rc = stage(X, (size_t)n, (size_t)d, (size_t)ldim, s, &F->loo_X, &F->loo_ld, &F->loo_Xown);
-   if (!rc) rc = stage(y, (size_t)n, 1, (size_t)n, s, &dy, &ldy, &F->loo_yown);
+   Scratch sc(s);
+   const double *dX, *dy;
+   long long ld, ldy;
+   int rc = stage(sc, X, (size_t)n, (size_t)d, (size_t)ldim, &dX, &ld);
+   if (!rc) rc = stage(sc, y, (size_t)n, 1, (size_t)n, &dy, &ldy);
    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;  // the host arrays may go after the call
+   if (rc) return rc;                                   // (the copies go with the call; nothing is bound)
+   if (dX != X) sc.trade(&F->loo_Xown, (double*)dX);    // the object keeps the copies
+   if (dy != y) sc.trade(&F->loo_yown, (double*)dy);
+   F->loo_X = dX;
+   F->loo_ld = ld;
    F->loo_y = dy;
-   if (rc) loo_unbind(F);
-   return rc;
+   return 0;
 }
 
 int Nfft4GPAmdFeatureGpLooLoss(void* fgp, double* x, double* lossp, double* dloss)
@@ -922,29 +856,19 @@ int Nfft4GPAmdFeatureGpLooPredict(void* fgp, double f, double l, double mu, doub
    FeatureGp* F = (FeatureGp*)fgp;
    if (!F || loo_ready(F, who, f)) return -1;
    hipStream_t s = current_stream();
+   Scratch sc(s);
    const size_t bytes = sizeof(double) * (size_t)F->n;
-   double* own[2] = {nullptr, nullptr};
    double* host[2] = {mean, var};
    double* dev[2] = {mean, var};
-   auto body = [&]() -> int {
-      for (int k = 0; k < 2; k++)
-         if (host[k] && !is_device_ptr(host[k])) {
-            NFFT4GP_HIP_CHECK(hipMalloc((void**)&own[k], bytes));
-            dev[k] = own[k];
-         }
-      double sums[kLooSums];
-      if (fgp_loo(F, f, l, mu, dev[0], dev[1], sums) || loo_outside(F, who, sums[5])) return -1;
-      for (int k = 0; k < 2; k++)
-         if (own[k]) NFFT4GP_HIP_CHECK(hipMemcpyAsync(host[k], own[k], bytes, hipMemcpyDeviceToHost, s));
-      F->loo_nonpositive = (long long)sums[4];
-      if (n_nonpositive) *n_nonpositive = F->loo_nonpositive;
-      return 0;
-   };
-   const int rc = body();
-   (void)hipStreamSynchronize(s);
-   for (double* p : own)
-      if (p) (void)hipFree(p);
-   return rc;
+   for (int k = 0; k < 2; k++)
+      if (host[k] && !is_device_ptr(host[k]) && sc.alloc(&dev[k], (size_t)F->n)) return -1;
+   double sums[kLooSums];
+   if (fgp_loo(F, f, l, mu, dev[0], dev[1], sums) || loo_outside(F, who, sums[5])) return -1;
+   for (int k = 0; k < 2; k++)
+      if (dev[k] != host[k]) NFFT4GP_HIP_CHECK(hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, s));
+   F->loo_nonpositive = (long long)sums[4];
+   if (n_nonpositive) *n_nonpositive = F->loo_nonpositive;
+   return sc.finish();
 }
 
 int Nfft4GPAmdFeatureGpLooStatus(void* fgp, long long* n_nonpositive)
@@ -956,12 +880,5 @@ int Nfft4GPAmdFeatureGpLooStatus(void* fgp, long long* n_nonpositive)
 }
 
 void Nfft4GPAmdFeatureGpFree(void* fgp) { fgp_free((FeatureGp*)fgp); }
-
-int Nfft4GPAmdModelFeatureWeightsGrad(int kernel, double l, double scale, int nw, double* dw33)
-{
-   if ((kernel != 0 && kernel != 1) || !(l > 0.0) || !(scale > 0.0) || nw < 1 || !dw33) return -1;
-   feature_weights_grad(kernel, l, scale, nw, dw33);
-   return 0;
-}
 
 }  // extern "C"

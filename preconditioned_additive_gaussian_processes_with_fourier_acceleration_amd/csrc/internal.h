@@ -505,32 +505,89 @@ hipStream_t current_stream();
 bool is_device_ptr(const void* p);
 int device_ok();
 
-// ---- the operator's finite-rank form with 1-D windows (model.hip, feature_gp.hip) ------------
+// ---- the operator's finite-rank form with 1-D windows (window_moments.hip, the model's files, feature_gp.hip;
+// DESIGN 3.16, 3.17) ----------------------------------------------------------------------------------------------
 // A = f^2 (Z W Z^T + mu I): per window 33 features [cos 2 pi k xs, k = 0..16 | sin 2 pi k xs, k = 1..16] of the
 // window's quantised coordinate; a window takes kMvPad slots and the windows are padded to a multiple of 4.
+// (what a kernel does with a point in a window -- the angle, the features, the domain test, the outside count -- is
+// window_points.hpp's)
 constexpr int kMvFeat = 33, kMvPad = 36, kMvMaxNw = 128;  // an R_p x R_p matrix at 128 windows: 170 MB
 constexpr double kMpLimit = 0.25 + 1.0 / 8589934592.0;    // the domain: |xs| <= 1/4 + 2^-33
 inline int mv_order(int nw) { return kMvPad * ((nw + 3) / 4 * 4); }  // R_p
+// the padded slot of feature i of the R = 33 nw unpadded ones
+__host__ __device__ inline int mv_slot(int i) { return i / kMvFeat * kMvPad + i % kMvFeat; }
 
-// cos and sin of 2 pi xs_q, xs_q the window's quantised coordinate (quantize(): what k_model_predict decodes its
-// cell and offset from); false when the point is outside the window's domain (the angle is then 0)
-__device__ inline bool mv_angle(double x, double ctr, double sc, double& c1, double& s1)
-{
-   const double xs = (x - ctr) * sc;
-   const bool in = fabs(xs) <= kMpLimit;
-   const double xq = in ? xs : 0.0;
-   const uint32_t q = (uint32_t)(unsigned long long)llround(xq * 4294967296.0);
-   sincospi((double)(int)q * (1.0 / 2147483648.0), &s1, &c1);  // |xs| <= 1/4: (int)q 2^-32 is xs_q
-   return in;
-}
+// A call's scratch allocations on stream s.  They are freed on every exit path, after the stream has drained if, and
+// only if, the call owns something: nothing in flight reads a buffer that goes, and a call that was handed device
+// arrays only returns without synchronising.
+struct Scratch {
+   hipStream_t s;
+   std::vector<void*> owned;
+   bool drained = false;
+   explicit Scratch(hipStream_t stream) : s(stream) {}
+   Scratch(const Scratch&) = delete;
+   Scratch& operator=(const Scratch&) = delete;
+   ~Scratch()
+   {
+      if (owns() && !drained) (void)hipStreamSynchronize(s);  // (error paths)
+      for (void* p : owned)
+         if (p) (void)hipFree(p);
+   }
+   // the call's last step: the stream drained if the call owns something, and what that reported; 0 or -1
+   int finish()
+   {
+      if (owns() && !drained) {
+         NFFT4GP_HIP_CHECK(hipStreamSynchronize(s));
+         drained = true;
+      }
+      return 0;
+   }
+   bool owns() const
+   {
+      for (void* p : owned)
+         if (p) return true;
+      return false;
+   }
+   // *p = count T on the device, owned by the call; 0 or -1
+   template <class T>
+   int alloc(T** p, size_t count)
+   {
+      *p = nullptr;
+      NFFT4GP_HIP_CHECK(hipMalloc((void**)p, sizeof(T) * count));
+      owned.push_back(*p);
+      return 0;
+   }
+   // *kept takes the call's buffer `mine`; what *kept held before (or nothing) goes with the call
+   template <class T>
+   void trade(T** kept, T* mine)
+   {
+      for (void*& p : owned)
+         if (p == (void*)mine) {
+            p = *kept;
+            *kept = mine;
+            return;
+         }
+   }
+};
+// a host or device array of rows x cols doubles (leading dimension ld) as a device array: *dev and *dld; a host array
+// is copied, packed, into scratch of the call (on its stream)
+int stage(Scratch& sc, const double* src, size_t rows, size_t cols, size_t ld, const double** dev, long long* dld);
 
-// (cos, sin) k theta -> (k + 1) theta: a rotation, whose error grows linearly in k (<= 16 steps)
-__device__ inline void mv_rotate(double& ck, double& sk, double c1, double s1)
-{
-   const double c = ck * c1 - sk * s1;
-   sk = sk * c1 + ck * s1;
-   ck = c;
-}
+// per-workgroup counts of the points outside the domain (window_points.hpp's block_count_outside writes them): a
+// device buffer that grows on demand and is read back and added on the host
+struct BlockCounts {
+   unsigned int* d = nullptr;
+   size_t cap = 0;
+   BlockCounts() = default;
+   BlockCounts(const BlockCounts&) = delete;
+   BlockCounts& operator=(const BlockCounts&) = delete;
+   ~BlockCounts()
+   {
+      if (d) (void)hipFree(d);
+   }
+   int grow(size_t nblk);                                   // room for nblk counts; 0 or -1
+   int read(size_t nblk, hipStream_t s, long long* total);  // copies nblk back, synchronises s, adds them; 0 or -1
+};
 
 // the windows of a handle or a model: device arrays of nw entries
 struct WindowMap {

@@ -1,7 +1,8 @@
 // quad_walk.hpp -- phi^T S phi for the 128 points of a workgroup on v_mfma_f64_16x16x4_f64, S symmetric R_p x R_p.
-// The body of k_model_std (model.hip), shared with k_fgp_loo (feature_gp.hip), which walks
-// three matrices one after another and also dots the points' features with NLIN coefficient vectors.  k_model_paths
-// (model.hip) takes the points, the feature generation and the buffers from here for Phi B.
+// The body of k_model_std (model_variance.hip), shared with k_fgp_loo (feature_gp.hip),
+// which walks three matrices one after another and also dots the points' features with NLIN coefficient vectors.
+// k_model_paths (model_paths.hip) takes the points, the feature generation and the buffers from here for
+// Phi B.  The features themselves are window_points.hpp's mv_features.
 //
 // One workgroup owns 128 points and walks S in column tiles of 144 (4 windows); per tile the product
 // Phi S[:, tile] (128 x 144) is accumulated over k steps of 36 (one window).  The Phi operand is generated into LDS
@@ -15,7 +16,7 @@
 // A point's sum runs over (tile, window, block, register) in a fixed order, then over its 4 lanes in lane order
 // (quad_fold): its bits depend on neither its place in the batch nor the batch size.
 #pragma once
-#include "internal.h"
+#include "window_points.hpp"
 
 namespace nfft4gp_amd {
 
@@ -54,23 +55,14 @@ template <int NLIN>
 __device__ inline void quad_gen(const QuadPoints& Q, int c, double x, int p, int part, double* As,
                                 const double* __restrict__ coef, int ldc, double* lin)
 {
-   double c1, s1;
-   (void)mv_angle(x, Q.centre[c], Q.scale[c], c1, s1);
-   double ck = 1.0, sk = 0.0;
+   (void)mv_features(x, Q.centre[c], Q.scale[c], [&](int j, double v) {
+      const int k = j <= 16 ? j : j - 16;
+      if (part == (j <= 16 ? 0 : 2) + (k <= 8 ? 0 : 1)) {
+         As[j * kMsLdA + p] = v;
 #pragma unroll
-   for (int k = 0; k <= 16; k++) {
-      if (part == (k <= 8 ? 0 : 1)) {
-         As[k * kMsLdA + p] = ck;
-#pragma unroll
-         for (int q = 0; q < NLIN; q++) lin[q] = fma(coef[(size_t)q * ldc + c * kMvPad + k], ck, lin[q]);
+         for (int q = 0; q < NLIN; q++) lin[q] = fma(coef[(size_t)q * ldc + c * kMvPad + j], v, lin[q]);
       }
-      if (k && part == (k <= 8 ? 2 : 3)) {
-         As[(16 + k) * kMsLdA + p] = sk;
-#pragma unroll
-         for (int q = 0; q < NLIN; q++) lin[q] = fma(coef[(size_t)q * ldc + c * kMvPad + 16 + k], sk, lin[q]);
-      }
-      mv_rotate(ck, sk, c1, s1);
-   }
+   });
 }
 
 // The lane's share of phi^T S phi for the point wm + lr of the workgroup (quad_fold adds the 4 lanes' shares).

@@ -1,4 +1,4 @@
-"""The fitted model's joint posterior sample paths (Nfft4GPAmdModelFitSampler / DrawPaths / EvalPaths, csrc/model.hip
+"""The fitted model's joint posterior sample paths (Nfft4GPAmdModelFitSampler / DrawPaths / EvalPaths, csrc/model_paths.hip
 k_model_paths; FittedModel.fit_sampler / draw_paths / paths / sample / path_curve):
 paths[i, s] = predict[i] + f sum_j phi_j(x_i) B[j, s], B = F xi, F F^T = S without its negative part.
 

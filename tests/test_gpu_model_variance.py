@@ -1,4 +1,4 @@
-"""The fitted model's predictive standard deviation (Nfft4GPAmdModelFitVariance / PredictStd, csrc/model.hip;
+"""The fitted model's predictive standard deviation (Nfft4GPAmdModelFitVariance / PredictStd, csrc/model_variance.hip;
 FittedModel.fit_variance / predict_std): std = sqrt|f^2 (mu + phi^T S phi)|, S = mu (mu I + W G)^{-1} W.
 
 Cases as in test_gpu_model.py: n = 1500, X ~ U[0,1)^nw with one 1-D window per feature, f = 1.3, mu = 0.01; 1000

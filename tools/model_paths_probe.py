@@ -7,11 +7,11 @@ training points), for ns = 1, 16, 64 and 256 paths:
      of the eigendecomposition);
   2. Nfft4GPAmdModelDrawPaths, xi on the device;
   3. Nfft4GPAmdModelEvalPaths, device pointers, no outside count: k_model_predict into a scratch vector, then
-     k_model_paths; against the fp64 matrix peak (78.6 TF) counted at 2 n_new R_p ns flops, R_p = 36 nw;
-  4. the composed route (Nfft4GPAmdDebugModelPaths, route 0): k_model_features into a chunk of Z, Z B on gemm_f64 and a
-     kernel that adds the mean, chunk by chunk, with the largest distance between the two routes' values.
+     k_model_paths; against the fp64 matrix peak (78.6 TF) counted at 2 n_new R_p ns flops, R_p = 36 nw.
 
-Both routes allocate their scratch (the mean; the composed route also Z and B) inside the timed call, as a caller sees it.
+The call allocates its scratch (the mean) inside the timed region, as a caller sees it.  The composed route that this
+probe once timed next to it (k_model_features into a chunk of Z, Z B on gemm_f64 and an add of the mean) lost at every
+count and was removed; its numbers are in profiles/model_paths_probe.json.
 
     python tools/model_paths_probe.py [--n 200000 --nw 32 --nnew 1000000 --reps 10 --fit-nw 32 64 --out FILE.json]
 """
@@ -101,7 +101,6 @@ def main():
     for ns in a.ns:
         xi = torch.tensor(rng.standard_normal((ns, R)), device="cuda")  # [ns][R]: column-major R x ns
         out = torch.empty((ns, nnew), dtype=torch.float64, device="cuda")
-        ref = torch.empty((ns, nnew), dtype=torch.float64, device="cuda")
         row = {"ns": ns}
 
         def draw():
@@ -111,22 +110,15 @@ def main():
         def fused():
             assert L.Nfft4GPAmdModelEvalPaths(model.h, Xd.data_ptr(), nnew, nnew, nw, -1, out.data_ptr(), nnew, None) == 0
 
-        def composed():
-            assert L.Nfft4GPAmdDebugModelPaths(model.h, Xd.data_ptr(), nnew, nnew, 0, ref.data_ptr(), nnew) == 0
-        # alternate the two routes' timings so that a drift of the machine touches both
         f1, _ = timed(fused, a.reps)
-        c1, _ = timed(composed, a.reps)
         f2, fbest = timed(fused, a.reps)
-        c2, cbest = timed(composed, a.reps)
         row["eval_paths_ms"], row["eval_paths_min_ms"] = min(f1, f2), fbest
-        row["composed_ms"], row["composed_min_ms"] = min(c1, c2), cbest
-        row["eval_paths_medians_ms"], row["composed_medians_ms"] = [f1, f2], [c1, c2]
+        row["eval_paths_medians_ms"] = [f1, f2]
         row["eval_paths_fraction_of_f64_matrix_peak"] = 2.0 * nnew * Rp * ns / (row["eval_paths_ms"] * 1e-3) / PEAK_F64_MATRIX
         row["output_GB"] = 8e-9 * nnew * ns
-        row["max_abs_fused_minus_composed"] = float((out - ref).abs().max())
         row["max_abs_value"] = float(out.abs().max())
         res["paths"].append(row)
-        del xi, out, ref
+        del xi, out
     model.free()
     print(json.dumps(res))
     if a.out:

@@ -914,6 +914,38 @@ int Nfft4GPAmdModelPredictStd(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new
  * nothing. */
 int Nfft4GPAmdModelPredictEffects(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, int w0, int wn,
                                   NFFT4GP_DOUBLE *effects, NFFT4GP_DOUBLE *effect_std, int ldo, long long *n_outside);
+/* ---- effects centred on a reference sample, the intercept and the windows' importances ----------
+ * Over a reference sample X_ref of n rows (the training points) the model keeps the features' means m = Z^T 1 / n
+ * (33 nw; every window's constant slot is exactly 1), each window's effect mean e_c = (1/n) sum_i e_ic and its
+ * standard deviation over the sample sd_c = sqrt((1/n) sum_i (e_ic - e_c)^2), e_ic the value
+ * Nfft4GPAmdModelPredictEffects gives for (row i, window c): sd_c is window c's importance, in the units of y.
+ * The centring belongs to the table and the sample: Nfft4GPAmdModelFitVariance / SetVariance keep it.
+ * Nfft4GPAmdModelFitCentring: X n x d column-major, leading dimension ldim, host or device.  Deterministic: two fits
+ * give the same bits whatever the pointers' kind and ldim.  0; -1 for a NULL model or X, d not the model's, n < 1 or
+ * ldim < n; -2 when a row lies outside the model's domain: the model, an earlier centring included, is unchanged. */
+int Nfft4GPAmdModelFitCentring(void *model, const NFFT4GP_DOUBLE *X, int n, int ldim, int d);
+/* what is held: *n_ref, feature_mean (33 nw, unpadded, the feature order of S), effect_mean (nw), effect_sd (nw);
+ * any pointer may be NULL.  -5 when the model holds no centring (nothing is written), -1 for a NULL model. */
+int Nfft4GPAmdModelCentring(void *model, int *n_ref, NFFT4GP_DOUBLE *feature_mean, NFFT4GP_DOUBLE *effect_mean,
+                            NFFT4GP_DOUBLE *effect_sd);
+/* the load path: the same arrays from the host.  -1 for a NULL model or array, n_ref < 1, nw not the model's, or a
+ * feature_mean[33 c] that is not exactly 1 */
+int Nfft4GPAmdModelSetCentring(void *model, int n_ref, const NFFT4GP_DOUBLE *feature_mean,
+                               const NFFT4GP_DOUBLE *effect_mean, const NFFT4GP_DOUBLE *effect_sd, int nw);
+/* Nfft4GPAmdModelPredictEffects with both arrays about the sample's means, every argument with the same meaning:
+ *   effects[(c - w0) ldo + i]    = fl(f^2 Horner) - e_c: the uncentred value minus effect_mean[c], bit for bit;
+ *   effect_std[(c - w0) ldo + i] = sqrt| f^2 (phi_c - m_c)^T S_cc (phi_c - m_c) |: slot 0 of phi_c - m_c is exactly 0,
+ *                                  so the shared constant's variance drops out whatever S_cc's first row holds.
+ * The mean is the intercept plus the sum of the centred effects, up to the rounding of the sums.  The domain rules
+ * and *n_outside are the uncentred call's.  -5 when the model holds no centring, -3 when effect_std is asked for
+ * and the model holds no variance, -1 as there.  A refused call writes nothing. */
+int Nfft4GPAmdModelPredictEffectsCentred(void *model, const NFFT4GP_DOUBLE *Xnew, int n_new, int ldim, int d, int w0,
+                                         int wn, NFFT4GP_DOUBLE *effects, NFFT4GP_DOUBLE *effect_std, int ldo,
+                                         long long *n_outside);
+/* *value = sum_c effect_mean[c], added in window order; *std (may be NULL, as may value) = sqrt| f^2 m^T S m | over
+ * the whole of m and S, without noise.  -5 without a centring, -3 when std is asked for and the model holds no
+ * variance, -1 for a NULL model; a refused call writes nothing. */
+int Nfft4GPAmdModelIntercept(void *model, NFFT4GP_DOUBLE *value, NFFT4GP_DOUBLE *std);
 /* wall clock of the model's last successful fit in ms: features, Grams and their sum, system + LU + symmetrise */
 int Nfft4GPAmdModelFitTimes(void *model, NFFT4GP_DOUBLE *ms3);
 /* *R = 33 nw when the model holds a variance, else 0 */

@@ -274,6 +274,12 @@ _SIGS = {
                                             C.POINTER(C.c_longlong)]),
     "Nfft4GPAmdModelPredictEffects": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
                                                 C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdModelFitCentring": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]),
+    "Nfft4GPAmdModelCentring": (C.c_int, [vp, ip, vp, vp, vp]),
+    "Nfft4GPAmdModelSetCentring": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int]),
+    "Nfft4GPAmdModelPredictEffectsCentred": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
+                                                       C.c_int, C.POINTER(C.c_longlong)]),
+    "Nfft4GPAmdModelIntercept": (C.c_int, [vp, dp, dp]),
     "Nfft4GPAmdModelVarianceInfo": (C.c_int, [vp, ip]),
     "Nfft4GPAmdModelFitTimes": (C.c_int, [vp, dp]),
     "Nfft4GPAmdModelVariance": (C.c_int, [vp, vp]),

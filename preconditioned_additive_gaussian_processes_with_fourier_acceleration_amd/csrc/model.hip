@@ -48,6 +48,7 @@ void model_free(Model* M)
 {
    if (!M) return;
    model_drop_sampler(M);
+   model_drop_centring(M);
    if (M->d_S) (void)hipFree(M->d_S);
    if (M->d_H) (void)hipFree(M->d_H);
    if (M->d_centre) (void)hipFree(M->d_centre);
@@ -224,17 +225,29 @@ __device__ inline void effects_quad(const double* blk, const double (&phi)[kPts]
    }
 }
 
-template <bool kStd>
+//
+// kCentred: both about the means over a reference sample.  The window's effect mean is subtracted from
+// the rounded product ff * v (two roundings, no contraction across them: the column is the uncentred column minus the
+// mean to the bit), and the window's 33 feature means, staged behind the group's S blocks, are subtracted from the
+// features once mv_features has delivered the thread's points and before effects_quad, into the registers the
+// features occupy anyway: slot 0 is 1 - 1 = 0 exactly, so the constant's variance never enters the form.  The
+// <., false> instantiations are instruction for instruction what they were before kCentred existed.
+// Measured at n_new = 1e6, 32 windows, alternating with the uncentred passes in one process (tools/
+// model_centring_probe.py, profiles/model_centring_probe.json): centred 108.2 us against 99.2 us, with std 1.386 ms
+// against 1.295 ms (7.1 %; the run's noise 6.5 us), 167 VGPRs against 164 at the same 3 waves per SIMD.
+template <bool kStd, bool kCentred>
 __global__ __launch_bounds__(kMpThreads) void k_model_effects(
    const double* __restrict__ H, const double* __restrict__ S, int Rp, const double* __restrict__ centre,
    const double* __restrict__ scale, const int* __restrict__ feature, int w0, int wn, const double* __restrict__ X,
    long long ldim, int n_new, double ff, double* __restrict__ effects, double* __restrict__ effect_std, long long lde,
-   long long lds, unsigned int* __restrict__ cnt_out)
+   long long lds, unsigned int* __restrict__ cnt_out, const double* __restrict__ emean,
+   const double* __restrict__ fmean)
 {
    constexpr int kPts = kStd ? kMePts : kMpPts;
    constexpr int kGroup = kStd ? kMeGroup : kMpGroup;
    __shared__ double s_H[kGroup * kMpWin];
-   __shared__ double s_S[kStd ? kGroup * kMeBlk : 1];
+   __shared__ double s_S[kStd ? kGroup * (kMeBlk + (kCentred ? kMvFeat : 0)) : 1];
+   [[maybe_unused]] double* const s_M = s_S + kGroup * kMeBlk;  // with kStd and kCentred: the group's feature means
    const int tid = threadIdx.x;
    const long long base = (long long)blockIdx.x * (kMpThreads * kPts) + tid;
    bool outside[kPts];
@@ -249,6 +262,9 @@ __global__ __launch_bounds__(kMpThreads) void k_model_effects(
             const int cl = i / kMeBlk, e = i - cl * kMeBlk, j = e / kMvFeat, k = e - j * kMvFeat;
             s_S[i] = S[((size_t)(c0 + cl) * kMvPad + j) * Rp + (size_t)(c0 + cl) * kMvPad + k];
          }
+      if constexpr (kStd && kCentred)
+         for (int i = tid; i < ng * kMvFeat; i += kMpThreads)
+            s_M[i] = fmean[(size_t)(c0 + i / kMvFeat) * kMvPad + i % kMvFeat];
       __syncthreads();
       for (int cl = 0; cl < ng; cl++) {
          const int c = c0 + cl;
@@ -266,7 +282,15 @@ __global__ __launch_bounds__(kMpThreads) void k_model_effects(
             const long long i = base + (long long)p * kMpThreads;
             const double v = table_eval(s_H + cl * kMpWin, (xv[p] - ctr) * sc, in[p]);
             outside[p] = outside[p] || !in[p];
-            if (effects && i < n_new) effects[(size_t)(c - w0) * (size_t)lde + i] = in[p] ? ff * v : __builtin_nan("");
+            if constexpr (kCentred) {
+               double e = ff * v;
+               asm volatile("" : "+v"(e));  // the product is rounded before the mean is subtracted
+               if (effects && i < n_new)
+                  effects[(size_t)(c - w0) * (size_t)lde + i] = in[p] ? e - emean[c] : __builtin_nan("");
+            } else {
+               if (effects && i < n_new)
+                  effects[(size_t)(c - w0) * (size_t)lde + i] = in[p] ? ff * v : __builtin_nan("");
+            }
          }
          if constexpr (kStd) {
             double phi[kPts][kMvFeat], quad[kPts];
@@ -274,6 +298,21 @@ __global__ __launch_bounds__(kMpThreads) void k_model_effects(
             for (int p = 0; p < kPts; p++) {
                (void)mv_features(xv[p], ctr, sc, [&](int j, double v) { phi[p][j] = v; });
                quad[p] = 0.0;
+            }
+            if constexpr (kCentred) {
+               const double* mc = s_M + cl * kMvFeat;
+#pragma unroll
+               for (int j = 0; j < kMvFeat; j++) {
+                  const double mj = mc[j];  // a broadcast read, shared by the thread's points
+#pragma unroll
+                  for (int p = 0; p < kPts; p++) {
+                     // phi - m in the feature's own register pair.  Written as phi[p][j] -= mj the allocator gives
+                     // every difference a fresh pair while the features are still live: 195 VGPRs and 2 waves per
+                     // SIMD; tied to its source it is 167 and 3, the uncentred kernel's shape.
+                     asm volatile("v_add_f64 %0, %0, -%1" : "+v"(phi[p][j]) : "v"(mj));
+                  }
+                  if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // at most 8 means in flight (effects_quad's rule)
+               }
             }
             effects_quad<kPts>(s_S + cl * kMeBlk, phi, quad);
 #pragma unroll
@@ -299,7 +338,7 @@ __global__ __launch_bounds__(kMpThreads) void k_model_effects(
 }  // namespace
 
 int model_predict_effects(Model* M, const double* Xnew, int n_new, long long ldim, int w0, int wn, double* effects,
-                          double* effect_std, long long ldo, long long* n_outside)
+                          double* effect_std, long long ldo, long long* n_outside, bool centred)
 {
    hipStream_t s = current_stream();
    Scratch sc(s);
@@ -333,10 +372,11 @@ int model_predict_effects(Model* M, const double* Xnew, int n_new, long long ldi
    if (n_outside && M->counts.grow(nblk)) return -1;
    unsigned int* cnt = n_outside ? M->counts.d : (unsigned int*)nullptr;
    const dim3 grid((unsigned int)nblk), block(kMpThreads);
-   auto* kern = effect_std ? k_model_effects<true> : k_model_effects<false>;
+   auto* kern = effect_std ? (centred ? k_model_effects<true, true> : k_model_effects<true, false>)
+                           : (centred ? k_model_effects<false, true> : k_model_effects<false, false>);
    hipLaunchKernelGGL(kern, grid, block, 0, s, (const double*)M->d_H, (const double*)M->d_S, mv_order(M->nw),
                       (const double*)M->d_centre, (const double*)M->d_scale, (const int*)M->d_feature, w0, wn, dX, ld,
-                      n_new, M->f * M->f, de, ds, lde, lds, cnt);
+                      n_new, M->f * M->f, de, ds, lde, lds, cnt, (const double*)M->d_emean, (const double*)M->d_fmean);
    NFFT4GP_HIP_CHECK(hipGetLastError());
    if (ehost)
       NFFT4GP_HIP_CHECK(hipMemcpy2DAsync(effects, sizeof(double) * (size_t)ldo, de, col, col, (size_t)wn,

@@ -1,5 +1,6 @@
-// model.hpp -- the fitted model's state and the few functions its three files call across each other: model.hip (the
-// table: lifetime, predict, effects), model_variance.hip (S and the predictive std), model_paths.hip (the sampler).
+// model.hpp -- the fitted model's state and the few functions its four files call across each other: model.hip (the
+// table: lifetime, predict, effects), model_variance.hip (S and the predictive std), model_paths.hip (the sampler),
+// model_centring.hip (the reference sample's means, the intercept).
 #pragma once
 #include <vector>
 
@@ -26,6 +27,12 @@ struct Model {
    int ns = 0, nsp = 0;
    double defect = 0.0, lam_min = 0.0, lam_max = 0.0;  // sum |lambda < 0| / sum |lambda| and S's extreme eigenvalues
    double sampler_ms = 0.0;                            // the eigendecomposition's wall clock
+   // the centring on a reference sample (model_centring.hip): it belongs to the table and the sample, not
+   // to S, so a new variance keeps it
+   double* d_fmean = nullptr;   // m = Z^T 1 / n_ref in S's slot layout: mv_order(nw), the padded slots zero; or none
+   double* d_emean = nullptr;   // [nw] the effects' means over the sample
+   std::vector<double> emean, esd;  // host copies: the effects' means and their standard deviations over the sample
+   int n_ref = 0;                   // the sample's rows; 0: no centring held
 };
 
 inline WindowMap window_map(const Model* M) { return WindowMap{M->nw, M->d, M->d_centre, M->d_scale, M->d_feature}; }
@@ -42,8 +49,11 @@ int to_device(T** dptr, const T* h, size_t count)
 void model_drop_sampler(Model* M);
 // the posterior mean at the rows of Xnew (host or device); *n_outside (may be NULL): the rows outside the domain
 int model_predict(Model* M, const double* Xnew, int n_new, long long ldim, double* mean, long long* n_outside);
-// the windows [w0, w0 + wn) one by one: their effects and, with effect_std, the effects' standard deviations
+// the windows [w0, w0 + wn) one by one: their effects and, with effect_std, the effects' standard deviations; centred:
+// both about the reference sample's means (the model holds a centring then)
 int model_predict_effects(Model* M, const double* Xnew, int n_new, long long ldim, int w0, int wn, double* effects,
-                          double* effect_std, long long ldo, long long* n_outside);
+                          double* effect_std, long long ldo, long long* n_outside, bool centred = false);
+// the centring goes (model_centring.hip)
+void model_drop_centring(Model* M);
 
 }  // namespace nfft4gp_amd

@@ -52,13 +52,6 @@ __global__ __launch_bounds__(256) void k_model_features(const double* __restrict
 // same bits every time.
 constexpr int kZyThreads = 256, kZyPts = 4;
 
-__device__ inline double zy_wave_sum(double v)
-{
-#pragma unroll
-   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-   return v;
-}
-
 __global__ __launch_bounds__(kZyThreads) void k_model_zty(const double* __restrict__ centre,
                                                           const double* __restrict__ scale,
                                                           const int* __restrict__ feature, int nw,

@@ -59,6 +59,15 @@ __device__ inline bool row_outside(const double* __restrict__ centre, const doub
    return out;
 }
 
+// the wave's sum of v in every lane, by a fixed butterfly: the same bits every time (k_model_zty, k_model_effect_moments,
+// k_model_intercept_parts)
+__device__ inline double zy_wave_sum(double v)
+{
+#pragma unroll
+   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+   return v;
+}
+
 // cnt_out[blockIdx.x] = the workgroup's number of points with bad[p] set, over its kThreads threads' kPts points each
 // (a ballot per point, a slot in LDS per wave, thread 0 adds the waves).  Every thread of the workgroup calls it;
 // cnt_out may be NULL (uniform): nothing is written then.

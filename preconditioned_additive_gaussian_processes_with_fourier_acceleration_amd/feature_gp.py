@@ -181,13 +181,13 @@ class FeatureGP:
             raise RuntimeError("Nfft4GPAmdFeatureGpMoments failed")
         return G, b, yy.value
 
-    def model(self, X, y, hyper, transform=0) -> FittedModel:
+    def model(self, X, y, hyper, transform=0, centring=False) -> FittedModel:
         """The fitted model at ``hyper``: sets the operator up there, solves in feature space, and returns
         FittedModel.from_operator(op, alpha) with S loaded -- no Krylov solve and no second Gram.  The model's table
         is the operator's (its matvec differs from the finite-rank form by the NFFT's 1e-8), and a table applied to
         the other form's alpha errs by that difference times |alpha|_1; so alpha takes one step of iterative
         refinement against the operator's own matvec: alpha += A^{-1} (y - op alpha), one matvec and one pass for
-        Z^T r."""
+        Z^T r.  ``centring=True`` also centres the model on X (FittedModel.fit_centring)."""
         import torch
         f, l, mu = self.transformed(hyper, transform)
         if self.op.setup(self.kernel, f=f, l=l, mu=mu) != 0:
@@ -201,6 +201,8 @@ class FeatureGP:
         if _lib.lib().Nfft4GPAmdModelSetVariance(m.h, S.ctypes.data, int(self.R)) != 0:
             m.free()
             raise RuntimeError("Nfft4GPAmdModelSetVariance failed (see stderr)")
+        if centring:
+            m.fit_centring(Xd)
         return m
 
     def free(self):

@@ -250,13 +250,15 @@ def _gp_fit_exact(L, op, X, lab, x0, steps, lr, beta1, beta2, eps, tol, transfor
 
 
 def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, transform=0, op=None, variance=False,
-             exact=False):
+             exact=False, centring=False):
     """The fitted model at the hyperparameters ``hyper`` = (f, l, mu) before the transform: sets the kernel up
     (Gaussian, or the kernel ``op`` was last set up with), solves f^2 (K + mu I) alpha = y with FGMRES on the
     device and returns FittedModel.from_operator(op, alpha).  ``op``: an NFFTAdditiveKernel over X to reuse.
     ``variance=True`` also fits the model's variance matrix on X, so that ``predict_std`` works, and
     ``predict_effects(..., std=True)`` / ``effect_curve(..., std=True)``: each window's term with its standard
     deviation (the terms alone need no variance).
+    ``centring=True`` also centres the model on X (FittedModel.fit_centring): ``predict_effects(..., centred=True)``,
+    ``intercept`` and ``importance``.
     ``exact=True`` (1-D windows): FeatureGP.model instead -- alpha from the feature-space solve and the variance
     matrix from the same factorisation, no FGMRES (tol, maxits and variance do not apply: S is always loaded)."""
     import torch
@@ -276,7 +278,7 @@ def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, tra
         _set_up_once(op, hyper, transform)
         fgp = FeatureGP(op, X, y)
         try:
-            return fgp.model(X, y, hyper, transform=transform)
+            return fgp.model(X, y, hyper, transform=transform, centring=centring)
         finally:
             fgp.free()
     L = _lib.lib()
@@ -293,4 +295,6 @@ def gp_model(X, windows, nwindows, dwindows, y, hyper, tol=1e-8, maxits=100, tra
     model = FittedModel.from_operator(op, alpha)
     if variance:
         model.fit_variance(X)
+    if centring:
+        model.fit_centring(X)
     return model

@@ -7,6 +7,9 @@ the training points were scaled to are refused (NaN).  ``fit_variance(X)`` adds 
 operator's finite-rank form, after which ``predict_std`` gives the predictive standard deviation the same way.
 The model is additive, f(x) = sum_c g_c(x_c): ``predict_effects`` gives each window's term and, with ``std=True``,
 its posterior standard deviation (S's diagonal blocks), and ``effect_curve`` one window's term along its own feature.
+``fit_centring(X)`` keeps the means of the features and of every window's term over the training points: after it
+``predict_effects(..., centred=True)`` gives the terms about those means with the std of the centred term (the
+shared constant's uncertainty drops out), ``intercept`` the one constant and ``importance`` the windows' ranking.
 ``draw_paths`` / ``paths`` / ``sample`` give joint draws of the latent function from the same S: a draw is a function,
 the same one at every point set it is evaluated at.
 """
@@ -102,6 +105,74 @@ class FittedModel:
         self.sampler_defect = None  # the factor of the previous S and its paths went with it
         return self
 
+    # ---- centring on a reference sample (Nfft4GPAmdModelFitCentring / Centring / Intercept) ----
+    def fit_centring(self, X):
+        """Centre the model on the reference sample X (n x d, numpy or a device tensor; the training points): keeps
+        the features' means, every window's effect mean and its standard deviation over the sample.  Afterwards
+        ``predict_effects(..., centred=True)``, ``intercept`` and ``importance`` work; ``fit_variance`` keeps the
+        centring.  A row outside the model's domain raises ValueError and leaves the model, an earlier centring
+        included, as it was."""
+        Xc, _, xp, _, ld, n, d = self._points(X)
+        if d != self.d:
+            raise ValueError(f"X has {d} columns; the model was fitted on {self.d}")
+        rc = _lib.lib().Nfft4GPAmdModelFitCentring(self.h, xp, int(n), int(ld), int(d))
+        if rc == -2:
+            raise ValueError("rows of X lie outside the model's domain (see stderr); the model is unchanged")
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelFitCentring failed with status {rc} (see stderr)")
+        return self
+
+    def _centring(self):
+        """(n_ref, feature_mean, effect_mean, effect_sd), or None when the model holds no centring"""
+        n_ref = C.c_int(0)
+        fm, em, sd = np.empty(33 * self.nw), np.empty(self.nw), np.empty(self.nw)
+        rc = _lib.lib().Nfft4GPAmdModelCentring(self.h, C.byref(n_ref), fm.ctypes.data, em.ctypes.data, sd.ctypes.data)
+        if rc == -5:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelCentring failed with status {rc}")
+        return n_ref.value, fm, em, sd
+
+    def _centring_or_raise(self):
+        held = self._centring()
+        if held is None:
+            raise RuntimeError("the model holds no centring: call fit_centring(X) first")
+        return held
+
+    @property
+    def has_centring(self) -> bool:
+        return _lib.lib().Nfft4GPAmdModelCentring(self.h, None, None, None, None) == 0
+
+    @property
+    def feature_mean(self):
+        """the 33 nw features' means over the reference sample, in S's feature order (every window's first is 1)"""
+        return self._centring_or_raise()[1]
+
+    @property
+    def effect_mean(self):
+        """every window's mean of its term over the reference sample (nw): what ``centred=True`` subtracts"""
+        return self._centring_or_raise()[2]
+
+    @property
+    def importance(self):
+        """every window's standard deviation of its term over the reference sample (nw), in the units of y: the
+        natural ranking of the windows"""
+        return self._centring_or_raise()[3]
+
+    def intercept(self, std: bool = False):
+        """The model's constant b = sum of ``effect_mean`` (added in window order), so that predict(x) = b + the sum
+        of the centred effects; ``std=True`` returns (b, std_b), std_b = sqrt|f^2 m^T S m| the posterior standard
+        deviation of the latent function's mean over the reference sample (needs ``fit_variance`` or a loaded S)."""
+        b, sb = C.c_double(0.0), C.c_double(0.0)
+        rc = _lib.lib().Nfft4GPAmdModelIntercept(self.h, C.byref(b), C.byref(sb) if std else None)
+        if rc == -5:
+            raise RuntimeError("the model holds no centring: call fit_centring(X) first")
+        if rc == -3:
+            raise RuntimeError("the model holds no variance: call fit_variance(X) first")
+        if rc != 0:
+            raise RuntimeError(f"Nfft4GPAmdModelIntercept failed with status {rc}")
+        return (b.value, sb.value) if std else b.value
+
     def predict_std(self, Xnew, strict: bool = True, noise: bool = True):
         """The predictive standard deviation sqrt|f^2 (mu + phi^T S phi)| at the rows of Xnew, with the conventions
         of ``predict``; ``noise=False`` drops the mu term.  Needs ``fit_variance`` (or a loaded S) first."""
@@ -118,7 +189,7 @@ class FittedModel:
         self._outside(nout, n_new, strict, "predict_std")
         return std
 
-    def predict_effects(self, Xnew, std: bool = False, strict: bool = True, window=None):
+    def predict_effects(self, Xnew, std: bool = False, strict: bool = True, window=None, centred: bool = False):
         """Each window's term of the posterior mean at the rows of Xnew: an (n_new, nw) array whose column c is
         f^2 times window c's table at the point's coordinate feature[c] -- the value ``predict`` adds for that window,
         so the columns sum to ``predict`` up to the rounding of one sum.  numpy gives a Fortran-ordered numpy array, a
@@ -130,7 +201,10 @@ class FittedModel:
         the windows asked for and ``strict`` raises on them, as in ``predict``.
 
         The constant is shared among the windows (each carries 1/nw of it) and the data identify only its sum, so a
-        window's raw std includes the constant's uncertainty; effects are not centred on the training data."""
+        window's raw std includes the constant's uncertainty.  ``centred=True`` (after ``fit_centring``) gives what a
+        plot of an additive model shows: column c minus ``effect_mean[c]``, bit for bit, and the std of that centred
+        term, sqrt|f^2 (phi_c - m_c)^T S_cc (phi_c - m_c)|, from which the constant's uncertainty has dropped out;
+        ``intercept`` holds the one constant."""
         if isinstance(Xnew, np.ndarray) or not hasattr(Xnew, "data_ptr"):
             X = np.asfortranarray(np.asarray(Xnew, dtype=np.float64))
             torch = None
@@ -158,22 +232,27 @@ class FittedModel:
         sd, sp = buffer() if std else (None, None)
         nout = C.c_longlong(0)
         xp = X.ctypes.data if torch is None else X.data_ptr()
-        rc = _lib.lib().Nfft4GPAmdModelPredictEffects(self.h, xp, int(n_new), max(int(n_new), 1), int(d), w0, wn, ep,
-                                                      sp, max(int(n_new), 1), C.byref(nout))
+        L = _lib.lib()
+        fn = L.Nfft4GPAmdModelPredictEffectsCentred if centred else L.Nfft4GPAmdModelPredictEffects
+        rc = fn(self.h, xp, int(n_new), max(int(n_new), 1), int(d), w0, wn, ep, sp, max(int(n_new), 1), C.byref(nout))
+        if rc == -5:
+            raise RuntimeError("the model holds no centring: call fit_centring(X) first")
         if rc == -3:
             raise RuntimeError("the model holds no variance: call fit_variance(X) first")
         if rc != 0:
-            raise RuntimeError(f"Nfft4GPAmdModelPredictEffects failed with status {rc}")
+            raise RuntimeError(f"Nfft4GPAmdModelPredictEffects{'Centred' if centred else ''} failed with status {rc}")
         self._outside(nout, n_new, strict, "predict_effects")
         if window is not None:
             eff, sd = eff[:, 0], (sd[:, 0] if std else None)
         return (eff, sd) if std else eff
 
-    def effect_curve(self, c, values, std: bool = False):
+    def effect_curve(self, c, values, std: bool = False, centred: bool = False):
         """Window c's term at the given values of its own feature (1-D, numpy or a torch device tensor), for plotting:
-        ``predict_effects(X, window=c)`` on an n x d input whose column feature[c] holds the values.  The raw std's
-        caveat about the shared constant applies (see ``predict_effects``)."""
-        return self.predict_effects(self._curve_points(c, values), std=std, strict=True, window=int(c))
+        ``predict_effects(X, window=c)`` on an n x d input whose column feature[c] holds the values.  The raw std
+        carries the shared constant's uncertainty; ``centred=True`` gives the centred term and its std (see
+        ``predict_effects``)."""
+        return self.predict_effects(self._curve_points(c, values), std=std, strict=True, window=int(c),
+                                    centred=centred)
 
     def _curve_points(self, c, values):
         """an n x d input (numpy, or a device tensor like ``values``) whose column feature[c] holds the values"""
@@ -265,8 +344,8 @@ class FittedModel:
         -- a draw of the latent function; observation noise is independent N(0, f^2 mu) per point, for the caller to
         add.  numpy gives a Fortran-ordered numpy array, a torch device tensor a device tensor (the transpose view of
         an (n_paths, n_new) buffer).  ``window=c`` gives window c's term of each path around
-        ``predict_effects(window=c)`` (only column feature[c] matters); the caveat about the shared constant from
-        ``predict_effects`` applies to one window's path.  A point outside the domain of a window that is summed is
+        ``predict_effects(window=c)`` (only column feature[c] matters); one window's path carries its share of the
+        constant and is not centred (``predict_effects(..., centred=True)`` is).  A point outside the domain of a window that is summed is
         NaN in every path; ``n_outside`` and ``strict`` behave as in ``predict_effects``."""
         if isinstance(Xnew, np.ndarray) or not hasattr(Xnew, "data_ptr"):
             X = np.asfortranarray(np.asarray(Xnew, dtype=np.float64))
@@ -307,11 +386,14 @@ class FittedModel:
 
     def path_curve(self, c, values):
         """Window c's term of every drawn path at the given values of its own feature (1-D, numpy or a torch device
-        tensor): ``effect_curve``'s twin, (n, n_paths).  The caveat about the shared constant applies."""
+        tensor): ``effect_curve``'s twin, (n, n_paths).  A window's path carries its share of the constant and stays
+        uncentred: subtract a path's mean over your own points, or see ``predict_effects(..., centred=True)`` for the
+        centred term and its std."""
         return self.paths(self._curve_points(c, values), window=int(c))
 
     def coefficients(self) -> dict:
-        """H (nw x 64 x 8), centre, scale, feature (nw each) and the scalars, as numpy arrays."""
+        """H (nw x 64 x 8), centre, scale, feature (nw each) and the scalars, as numpy arrays; S when a variance is
+        held; feature_mean, effect_mean, effect_sd and n_ref when a centring is."""
         H = np.empty((self.nw, _NCELL, _NC))
         centre, scale = np.empty(self.nw), np.empty(self.nw)
         feature = np.empty(self.nw, dtype=np.int32)
@@ -326,10 +408,14 @@ class FittedModel:
             if _lib.lib().Nfft4GPAmdModelVariance(self.h, S.ctypes.data) != 0:
                 raise RuntimeError("Nfft4GPAmdModelVariance failed")
             co["S"] = S  # features per window: cos 2 pi k xs, k = 0..16, then sin 2 pi k xs, k = 1..16
+        held = self._centring()
+        if held is not None:
+            co["n_ref"], co["feature_mean"], co["effect_mean"], co["effect_sd"] = held
         return co
 
     @classmethod
-    def from_coefficients(cls, H, centre, scale, feature, d, kernel, hyper, S=None) -> "FittedModel":
+    def from_coefficients(cls, H, centre, scale, feature, d, kernel, hyper, S=None, centring=None) -> "FittedModel":
+        """``centring``: a dict with ``coefficients()``' keys n_ref, feature_mean, effect_mean and effect_sd."""
         H = np.ascontiguousarray(H, dtype=np.float64)
         centre = np.ascontiguousarray(centre, dtype=np.float64)
         scale = np.ascontiguousarray(scale, dtype=np.float64)
@@ -349,6 +435,15 @@ class FittedModel:
                 raise ValueError("S must be 33 nw x 33 nw")
             if _lib.lib().Nfft4GPAmdModelSetVariance(m.h, S.ctypes.data, int(S.shape[0])) != 0:
                 raise RuntimeError("Nfft4GPAmdModelSetVariance failed (see stderr)")
+        if centring is not None:
+            fm, em, sd = (np.ascontiguousarray(centring[k], dtype=np.float64)
+                          for k in ("feature_mean", "effect_mean", "effect_sd"))
+            if fm.shape != (33 * nw,) or em.shape != (nw,) or sd.shape != (nw,):
+                raise ValueError("centring: feature_mean must hold 33 nw values, effect_mean and effect_sd nw each")
+            if _lib.lib().Nfft4GPAmdModelSetCentring(m.h, int(centring["n_ref"]), fm.ctypes.data, em.ctypes.data,
+                                                     sd.ctypes.data, int(nw)) != 0:
+                raise RuntimeError("Nfft4GPAmdModelSetCentring failed: n_ref >= 1 and every window's first "
+                                   "feature_mean exactly 1")
         return m
 
     def save(self, path):
@@ -358,8 +453,12 @@ class FittedModel:
     @classmethod
     def load(cls, path) -> "FittedModel":
         with np.load(path) as z:
+            centring = None
+            if "n_ref" in z.files:
+                centring = {k: z[k] for k in ("n_ref", "feature_mean", "effect_mean", "effect_sd")}
             return cls.from_coefficients(z["H"], z["centre"], z["scale"], z["feature"], int(z["d"]),
-                                         int(z["kernel"]), z["hyper"], S=z["S"] if "S" in z.files else None)
+                                         int(z["kernel"]), z["hyper"], S=z["S"] if "S" in z.files else None,
+                                         centring=centring)
 
     def free(self):
         if getattr(self, "h", None):

@@ -1,4 +1,4 @@
-"""Quadrature probes in pairs (krylov.hip lanczos_pair_dev): Nfft4GPLanczosQuadratureLogdet on this
+"""Quadrature probes in pairs (lanczos.hip lanczos_pair_dev): Nfft4GPLanczosQuadratureLogdet on this
 library's additive operator runs caller-given probes two at a time, sharing each Lanczos step's matvec
 through the two-vector interpolation.  Per-step printing (print_level 1) keeps the one-probe-at-a-time
 loop, so the two paths are compared directly: loss and gradient to 1e-10 (the two-vector kernels sum in
